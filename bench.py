@@ -18,6 +18,13 @@ Rank 0 prints ONE JSON line carrying `roofline` (HBM: algorithmic bytes / measur
 roofline of this integer path against both the guide's 2-cycle ceiling and the opcode-mix ceiling) and `cpu_baseline`
 (the CPU oracle on a bounded sample: the hand-written AVX2 u8 anti-diagonal restatement for cfg2/cfg4 with the other
 restatements and a thread-scaling line beside it, the scalar restatement elsewhere).
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, --dump-outputs, the line.  Everything
+else runs with --full: the parity gates against the CPU oracle, the overlapped-passes figure, the host end-to-end time, the live
+counter passes, `cpu_baseline`, the strong-scaling figure of a multi-rank weak run and (default cfg2 run) `all_configs`; without
+--full those fields are null.  --dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float64;
+arrays over the 64 MB budget as a seeded sample of rows, with the row numbers in DIR/<name>_rows.npy); inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -89,7 +96,40 @@ def parse_args():
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed passes for this long BEFORE the W warm-up steps: the input set-up on the host leaves the GPU idle for "
                          "seconds and its clocks take longer than a handful of 0.4 ms passes to come back (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: parity gates against the CPU oracle, the overlapped-passes figure, "
+                         "end_to_end_ms, the live counter passes, cpu_baseline, strong_scaling (multi-rank weak run) and all_configs (default run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float64, at most 64 MB)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64_000_000        # bytes of .npy data --dump-outputs may write in all
+
+
+def dump_outputs(path, arrays, suffix=""):
+    """arrays: {name: integer numpy array or torch tensor} -> path/<name><suffix>.npy as float64 (exact for these integers).  Smallest
+    first, each array gets an equal share of what is left of DUMP_BUDGET; one that does not fit is cut to a seeded sample of its rows,
+    whose indices go to <name>_rows<suffix>.npy."""
+    os.makedirs(path, exist_ok=True)
+    size = lambda a: int(np.prod(a.shape))
+    arrays = sorted(arrays.items(), key=lambda x: size(x[1]))
+    left = DUMP_BUDGET - 4096 * 2 * len(arrays)            # (.npy headers)
+    for i, (nm, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        if size(a) * 8 > share:
+            row_bytes = 8 * (size(a) // max(a.shape[0], 1)) + 8
+            rows = np.sort(np.random.default_rng(0xD0).choice(a.shape[0], size=share // row_bytes, replace=False))
+            np.save(os.path.join(path, nm + "_rows" + suffix + ".npy"), rows.astype(np.float64))
+            if isinstance(a, np.ndarray):
+                a = a[rows]
+            else:
+                import torch
+                a = a[torch.from_numpy(rows).to(a.device)]
+            left -= 8 * rows.size
+        a = a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        np.save(os.path.join(path, nm + suffix + ".npy"), a.astype(np.float64))
+        left -= 8 * a.size
 
 
 def self_launch(args):
@@ -158,18 +198,21 @@ def single_process(args):
         n_cfg = args.pairs or n_cfg
         n = n_cfg if strong else n_cfg * N
         a, b = Dg.pairs_random(0x7A00 + 2, n, L)
-        # parity gate: a side batch of mutated pairs through the HOST entry (the fan-out, the chunked staging, the gather) ...
-        am, bm = Dg.pairs_mutated_fixed(0x5EED, 4096, L, (k // max(costs[0], costs[1])) or 1, swaps=costs[3] is not None)
-        want_m = O.levenshtein_k_batch(O.csr_from_fixed(am), O.csr_from_fixed(bm), k, costs)
-        os.environ.setdefault("TA_MULTI_MIN_PAIRS", "256")            # (TA_TUNING only: lets the 4,096-pair side batch reach every device)
-        assert np.array_equal(M.levenshtein_k_batch_host(am, bm, k, costs), want_m), "parity gate failed: host fan-out != oracle"
-        os.environ.pop("TA_MULTI_MIN_PAIRS", None)
         S = M.ShardedPairs(a, b, N)
-        got = S.levenshtein_k(k, costs)                               # ... and the resident handle on the timed batch
-        ns = min(n, 4000)
-        assert np.array_equal(got[:ns], O.levenshtein_k_batch(O.csr_from_fixed(a[:ns]), O.csr_from_fixed(b[:ns]), k, costs)), "parity gate failed"
-        tail = slice(max(0, n - 1000), n)
-        assert np.array_equal(got[tail], O.levenshtein_k_batch(O.csr_from_fixed(a[tail]), O.csr_from_fixed(b[tail]), k, costs)), "parity gate failed (last shard)"
+        parity_some = None
+        if args.full:
+            # parity gate: a side batch of mutated pairs through the HOST entry (the fan-out, the chunked staging, the gather) ...
+            am, bm = Dg.pairs_mutated_fixed(0x5EED, 4096, L, (k // max(costs[0], costs[1])) or 1, swaps=costs[3] is not None)
+            want_m = O.levenshtein_k_batch(O.csr_from_fixed(am), O.csr_from_fixed(bm), k, costs)
+            os.environ.setdefault("TA_MULTI_MIN_PAIRS", "256")            # (TA_TUNING only: lets the 4,096-pair side batch reach every device)
+            assert np.array_equal(M.levenshtein_k_batch_host(am, bm, k, costs), want_m), "parity gate failed: host fan-out != oracle"
+            os.environ.pop("TA_MULTI_MIN_PAIRS", None)
+            got = S.levenshtein_k(k, costs)                               # ... and the resident handle on the timed batch
+            ns = min(n, 4000)
+            assert np.array_equal(got[:ns], O.levenshtein_k_batch(O.csr_from_fixed(a[:ns]), O.csr_from_fixed(b[:ns]), k, costs)), "parity gate failed"
+            tail = slice(max(0, n - 1000), n)
+            assert np.array_equal(got[tail], O.levenshtein_k_batch(O.csr_from_fixed(a[tail]), O.csr_from_fixed(b[tail]), k, costs)), "parity gate failed (last shard)"
+            parity_some = int((want_m != 0xFFFFFFFF).sum())
         cells_total = O.band_cells(L, L, k, costs) * n
         bytes_total = (2 * L + 4) * n
         if args.prewarm_ms > 0:
@@ -180,16 +223,19 @@ def single_process(args):
         t0 = t_wall()
         dev_ms = S.time_levenshtein_k(k, costs, steps=args.steps) / args.steps      # the slowest shard's device time (HIP events on its worker's stream)
         elapsed = t_wall() - t0                                                     # dispatch to the workers + the passes + their synchronisation
-        ts = []
-        for _ in range(4):
-            t1 = t_wall()
-            M.levenshtein_k_batch_host(a, b, k, costs)
-            ts.append((t_wall() - t1) * 1e3)
-        e2e_ms = float(np.median(ts[1:]))
+        if args.dump_outputs:          # (the timing entry returns no answers: the same pass over the same resident handle, once more)
+            dump_outputs(args.dump_outputs, {"distances": S.levenshtein_k(k, costs)})
+        e2e_ms = None
+        if args.full:
+            ts = []
+            for _ in range(4):
+                t1 = t_wall()
+                M.levenshtein_k_batch_host(a, b, k, costs)
+                ts.append((t_wall() - t1) * 1e3)
+            e2e_ms = float(np.median(ts[1:]))
         shards = S.n_shards
         S.close()
         desc, unit_name, units = "%s geometry: k=%d, %d random %dB pairs" % (wl, k, n, L), "pairs", n
-        parity_some = int((want_m != 0xFFFFFFFF).sum())
     elif wl == "cfg5":
         mib = args.pairs or 1024
         size = (mib << 20) if strong else (mib << 20) * N
@@ -201,24 +247,26 @@ def single_process(args):
             mm = np.frombuffer(Dg.mutate(g, needle, 10), dtype=np.uint8)
             hay_np[pos:pos + mm.size] = mm
         H = M.ShardedHaystack(hay_np, overlap=4096, n_shards=N)
-        # parity: the sharded All-mode result's records inside every shard cut's neighbourhood and at the front, against the oracle run on
-        # those windows; Best == the fold over the All-mode hits
-        all_hits = [tuple(m) for m in H.levenshtein_search(needle, k, T.SearchType.All, costs)]
-        ns = min(size, 4 << 20)
-        want = O.levenshtein_search_naive_with_opts(needle, hay_np[:ns].tobytes(), k, O.ALL, costs, False)
-        assert [h for h in all_hits if h[1] <= ns] == [w for w in want if w[1] > 0], "parity gate failed: sharded search != oracle (front)"
-        parity_some = len(want)
-        for r in range(1, N):
-            cut = size * r // N
-            lo, hi = max(0, cut - (1 << 20) - 4096), min(size, cut + (1 << 20))
-            w = O.levenshtein_search_naive_with_opts(needle, hay_np[lo:hi].tobytes(), k, O.ALL, costs, False)
-            w = [(s0 + lo, e0 + lo, kk) for s0, e0, kk in w if e0 > 4096 or lo == 0]
-            gotw = [h for h in all_hits if lo + (4096 if lo else 0) < h[1] <= hi]
-            assert gotw == [x for x in w if x[1] > 0], "parity gate failed: sharded search != oracle across cut %d" % r
-            parity_some += len(w)
-        from triple_accel_amd import dist as TD
-        best = [tuple(m) for m in H.levenshtein_search(needle, k, T.SearchType.Best, costs)]
-        assert best == TD.fold_best(all_hits, k, True), "parity gate failed: Best != fold over the All-mode hits"
+        parity_some = None
+        if args.full:
+            # parity: the sharded All-mode result's records inside every shard cut's neighbourhood and at the front, against the oracle run
+            # on those windows; Best == the fold over the All-mode hits
+            all_hits = [tuple(m) for m in H.levenshtein_search(needle, k, T.SearchType.All, costs)]
+            ns = min(size, 4 << 20)
+            want = O.levenshtein_search_naive_with_opts(needle, hay_np[:ns].tobytes(), k, O.ALL, costs, False)
+            assert [h for h in all_hits if h[1] <= ns] == [w for w in want if w[1] > 0], "parity gate failed: sharded search != oracle (front)"
+            parity_some = len(want)
+            for r in range(1, N):
+                cut = size * r // N
+                lo, hi = max(0, cut - (1 << 20) - 4096), min(size, cut + (1 << 20))
+                w = O.levenshtein_search_naive_with_opts(needle, hay_np[lo:hi].tobytes(), k, O.ALL, costs, False)
+                w = [(s0 + lo, e0 + lo, kk) for s0, e0, kk in w if e0 > 4096 or lo == 0]
+                gotw = [h for h in all_hits if lo + (4096 if lo else 0) < h[1] <= hi]
+                assert gotw == [x for x in w if x[1] > 0], "parity gate failed: sharded search != oracle across cut %d" % r
+                parity_some += len(w)
+            from triple_accel_amd import dist as TD
+            best = [tuple(m) for m in H.levenshtein_search(needle, k, T.SearchType.Best, costs)]
+            assert best == TD.fold_best(all_hits, k, True), "parity gate failed: Best != fold over the All-mode hits"
         run = lambda: H.levenshtein_search(needle, k, T.SearchType.Best, costs)
         t1 = t_wall()
         while (t_wall() - t1) * 1e3 < args.prewarm_ms:
@@ -227,11 +275,13 @@ def single_process(args):
             run()
         t0 = t_wall()
         for _ in range(args.steps):
-            run()
+            last = run()
         elapsed = t_wall() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"best": np.array([tuple(int(v) for v in m) for m in last], dtype=np.int64).reshape(-1, 3)})
         dev_ms = None
         ts = []
-        hay_bytes = hay_np.tobytes() if size <= (2 << 30) else None
+        hay_bytes = hay_np.tobytes() if size <= (2 << 30) and args.full else None
         for _ in range(3 if hay_bytes else 0):
             t1 = t_wall()
             list(T.levenshtein_search_simd_with_opts(needle, hay_bytes, k, T.SearchType.Best, T.EditCosts(*costs), False))
@@ -496,8 +546,17 @@ def main():
                     for i in range(min(n, 600)):
                         wd, we = O.levenshtein_simd_k_with_opts(fixed[0][lo + i].tobytes(), fixed[1][lo + i].tobytes(), k, True, costs)
                         assert scripts[i] == (we if wd is not None else []), "parity gate failed: edit script != oracle's traceback"
-                    extra_t["runs_total"] = int(ne.to(torch.int64).sum().item())
                 return ns
+
+            def outputs():
+                """what the timed pass hands its caller; the record slots a script does not fill are zeroed (never written by the pass)"""
+                if wl not in ("cfg2t", "cfg2tp"):
+                    return {"distances": out}
+                slot = torch.arange(cap, device="cuda")[None, :]
+                used = ne.clamp(max=cap)[:, None]
+                if wl == "cfg2t":
+                    return {"distances": out, "n_edits": ne, "edits": torch.where((slot < used)[:, :, None], ed, 0)}
+                return {"distances": out, "n_edits": ne, "packed": torch.where(slot >= cap - used, ed, 0)}
 
             def end_to_end(reps=5):
                 """host buffers in, answers out: pinned H2D of the batch + the pass + D2H of the results; ms (median)"""
@@ -514,7 +573,10 @@ def main():
                     torch.cuda.synchronize()
                     ts.append((time.perf_counter() - t1) * 1e3)
                 return float(np.median(ts[1:]))
-            extra_t = {"csr": csr, "oracle": oracle, "cells_total": cells_total, "bytes_total": bytes_total, "end_to_end": end_to_end}
+            extra_t = {"csr": csr, "oracle": oracle, "cells_total": cells_total, "bytes_total": bytes_total, "end_to_end": end_to_end,
+                       "outputs": outputs}
+            if wl in ("cfg2t", "cfg2tp"):
+                extra_t["runs_total"] = lambda: int(ne.to(torch.int64).sum().item())
             if n and wl in ("cfg2", "cfg4", "cfg2w", "cfg4w", "cfg2l", "cfg2s"):
                 extra_t["run_alt"], extra_t["out_pair"] = run_alt, (out, out_b)
             return run, n, parity, extra_t
@@ -566,7 +628,7 @@ def main():
                     ts.append((time.perf_counter() - t1) * 1e3)
                 return float(np.median(ts[1:]))
             return run, hay_np.size, parity, {"hay_np": hay_np, "cells_total": cells_unit * hay_np.size, "bytes_total": bytes_unit * hay_np.size,
-                                              "end_to_end": end_to_end}
+                                              "end_to_end": end_to_end, "outputs": lambda: {"hits": holder["hits"]}}
     else:   # cfg5: levenshtein_search, 32 B needle over a 1 GiB random shard per GPU
         mib = args.pairs or 1024
         needle = Dg.random_bytes(Dg.rng(0x7A05), 32).tobytes()     # same needle on every rank
@@ -632,7 +694,8 @@ def main():
                     torch.cuda.synchronize()
                     ts.append((time.perf_counter() - t1) * 1e3)
                 return float(np.median(ts[1:]))
-            extra_t = {"hay_np": hay_np, "cells_total": cells_unit * hay_np.size, "bytes_total": bytes_unit * hay_np.size, "end_to_end": end_to_end}
+            extra_t = {"hay_np": hay_np, "cells_total": cells_unit * hay_np.size, "bytes_total": bytes_unit * hay_np.size, "end_to_end": end_to_end,
+                       "outputs": lambda: {"best": np.array([tuple(int(v) for v in m) for m in holder["best"]], dtype=np.int64).reshape(-1, 3)}}
             return run, hay_np.size, parity, extra_t
 
     # ------------------------------------------------------------------ timing helpers
@@ -724,19 +787,21 @@ def main():
                  and not args.early_out)
     launch_mode = {}
     run, units, parity, extra = make(strong and world > 1)
-    parity_n = parity()
+    parity_n = parity() if args.full else None
     parity_some, parity_side = extra.get("parity_some"), extra.get("parity_side", 0)
-    if wl in ("cfg2t", "cfg2tp"):      # algorithmic bytes of a traceback pass: the strings, the distance and run count per pair, the runs written (16 / 4 B each)
-        extra["bytes_total"] += 4 * units + (16 if wl == "cfg2t" else 4) * extra["runs_total"]
-    info = T.last_launch_info()
-    kernel_name = T.last_kernel_name()
     elapsed, dev_ms, n_ramp = timed_region(run, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, extra["outputs"](), "_rank%d" % rank if world > 1 else "")
+    info = T.last_launch_info()                       # (the timed batch's: every launch since make() was one of its passes)
+    kernel_name = T.last_kernel_name()
+    if wl in ("cfg2t", "cfg2tp"):      # algorithmic bytes of a traceback pass: the strings, the distance and run count per pair, the runs written (16 / 4 B each)
+        extra["bytes_total"] += 4 * units + (16 if wl == "cfg2t" else 4) * extra["runs_total"]()
     # A second, DISCLOSED figure (never `value`): the same K passes with consecutive passes on TWO streams (one graph, fork / join inside the
     # capture, two output buffers).  A pass costs whole wavefronts per SIMD (15.26 per SIMD cost 16) and its first resident set waits for its
     # first lines together (~17 us): neither can be recovered INSIDE a pass, but a caller with batches in flight on two
     # streams lets the next pass's head fill this pass's tail.  Measured in the same process right after the timed region.
     overlapped = None
-    if graphable and not args.no_graph and world == 1 and extra.get("run_alt") and args.steps >= 2:
+    if args.full and graphable and not args.no_graph and world == 1 and extra.get("run_alt") and args.steps >= 2:
         try:
             run_alt = extra["run_alt"]
             run_alt(); torch.cuda.synchronize()
@@ -768,11 +833,11 @@ def main():
             print("bench.py: overlapped-passes figure failed (%s: %s)" % (type(e).__name__, e), file=sys.stderr)
             torch.cuda.synchronize()
     all_units, all_cells = totals(units, extra["cells_total"])
-    e2e_ms = extra["end_to_end"]() if world == 1 else None
+    e2e_ms = extra["end_to_end"]() if args.full and world == 1 else None
 
     strong_fig = None
     extra_bytes = extra["bytes_total"]
-    if world > 1 and not strong:        # the second figure of a multi-rank weak run: the same batch partitioned over the ranks
+    if args.full and world > 1 and not strong:        # the second figure of a multi-rank weak run: the same batch partitioned over the ranks
         del run, parity, extra
         torch.cuda.empty_cache()
         run_s, units_s, parity_s, extra_s = make(True)
@@ -849,7 +914,7 @@ def main():
         pmc = None
     # measured in THIS run where rocprofv3 is on the box: scripts/pmc_collect.py (separate --pmc passes around this same command, 3 steps)
     under_profiler = any(k.startswith(("ROCPROF", "ROCP_", "ROCTRACER", "RPD_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if not args.no_pmc and world == 1 and not dist_on and not under_profiler:       # (never a profiler inside a profiler)
+    if args.full and not args.no_pmc and world == 1 and not dist_on and not under_profiler:       # (never a profiler inside a profiler)
         import shutil
         import tempfile
         if shutil.which("rocprofv3"):
@@ -886,7 +951,7 @@ def main():
             pass
 
     cpu = None
-    if not args.no_cpu and world == 1:        # the CPU leg runs at N = 1 only (rank 0)
+    if args.full and not args.no_cpu and world == 1:        # the CPU leg runs at N = 1 only (rank 0)
         facts = host_cpu_facts()
 
         def timed(fn, min_s=3.0, max_reps=64):
@@ -1023,7 +1088,7 @@ def main():
                      "note": "integer VALU-issue-bound path (DESIGN.md section 5); the HBM fraction is reported because north_star asks for it"},
         "cpu_baseline": cpu,
         "timed_region": launch_mode.get("mode"),
-        "kernel": info, "parity_checked_units": parity_n + parity_side,
+        "kernel": info, "parity_checked_units": parity_n + parity_side if args.full else None,
         # how many of the answers compared with the oracle before the timed region were Some(d) -- random pairs at these k are all None,
         # so the gate also runs a side batch of mutated pairs of the same geometry through the same entry point (parity_side_batch)
         "parity_checked_some": parity_some, "parity_side_batch": parity_side,
@@ -1032,7 +1097,7 @@ def main():
     # (four of five configs were builder-run claims.)  The default invocation keeps cfg2 as the headline -- everything above --
     # and then times cfg4, cfg5 (1 GiB), cfg3 and cfg1 each in its own bench.py process: its own parity gate, fewer steps, its own live
     # counter passes.  Their figures ride in `all_configs`; a leg that fails reports its error and the line is printed regardless.
-    if wl == "cfg2" and world == 1 and not dist_on and args.dist == "random" and not args.no_all_configs and not args.no_pmc and \
+    if args.full and wl == "cfg2" and world == 1 and not dist_on and args.dist == "random" and not args.no_all_configs and not args.no_pmc and \
             not args.early_out and not args.unit_prefilter and not args.pairs and not under_profiler:
         rows = [{"workload": line["config"]["workload"], "ms_per_step": line["ms_per_step"], "value": value, "unit": "GCUPS",
                  "roofline_frac": achieved / HBM_PEAK_GBS, "cycles_per_valu_inst": (valu_issue or {}).get("cycles_per_valu_inst_per_simd"),
@@ -1044,7 +1109,7 @@ def main():
             row = {"workload": leg}
             try:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", leg, "--steps", str(leg_steps), "--warmup", "2",
-                                    "--no-cpu", "--no-all-configs", "--prewarm-ms", "150"], capture_output=True, text=True, timeout=420)
+                                    "--no-cpu", "--no-all-configs", "--prewarm-ms", "150", "--full"], capture_output=True, text=True, timeout=420)
                 js = [l for l in r.stdout.splitlines() if l.startswith("{")]
                 if r.returncode != 0 or not js:
                     raise RuntimeError("rc %d: %s" % (r.returncode, r.stderr[-300:]))

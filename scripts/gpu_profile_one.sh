@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 tag=$1; shift
 O=$GRAFT_REPO_ROOT/gpurun_out/profiles; mkdir -p $O
 cd $GRAFT_REPO_ROOT
-timeout 900 python bench.py "$@" --steps 50 --no-cpu --no-pmc > $O/bench_$tag.json 2>/dev/null
+timeout 900 python bench.py "$@" --steps 50 --no-cpu --no-pmc --full > $O/bench_$tag.json 2>/dev/null
 (cd /tmp; rm -rf /tmp/kt_$tag; rocprofv3 --kernel-trace --stats -d /tmp/kt_$tag -o kt -f csv -- python $GRAFT_REPO_ROOT/bench.py "$@" --steps 5 --warmup 1 --no-cpu --no-pmc 2>/dev/null | grep '^{' > $O/bench_${tag}_under_kernel_trace.json; cp $(find /tmp/kt_$tag -name "kt_kernel_stats.csv" | head -1) $O/bench_${tag}_kernel_stats.csv; rm -rf /tmp/kt_$tag)
 wl=$(echo "$@" | sed -n 's/.*--workload \([a-z0-9]*\).*/\1/p'); [ -z "$wl" ] && wl=cfg2
 extra=$(echo "$@" | sed 's/--workload [a-z0-9]*//')

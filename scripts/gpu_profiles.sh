@@ -34,11 +34,11 @@ steps() { case $1 in cfg3) echo "--steps 3 --warmup 1" ;; cfg5|hsearch*|cfg2t) e
 TAGS="cfg2 cfg2_mutated cfg4 cfg1 cfg5 cfg3 cfg2w cfg4w cfg2l cfg2s cfg2t cfg2_ragged cfg2_ragged_vline cfg2_dna cfg2_dna5 cfg2_protein_table hsearch8 hsearch32 hsearch64"
 envof() { case $1 in cfg2_ragged_vline) echo "TA_TUNING=1 TA_BITS_VLINE=1" ;; cfg2_protein_table) echo "TA_TUNING=1 TA_BITSQ_WIDE=1" ;; *) echo "TA_NOENV=1" ;; esac; }
 for tag in $TAGS; do
-  nocpu="--no-cpu --no-pmc"; [ $tag = cfg2 ] && nocpu=""       # (cfg2: the driver's command -- cpu_baseline leg and the live counter passes included)
-  env $(envof $tag) timeout 900 python bench.py $(flags $tag) $(steps $tag) $nocpu > $O/bench_$tag.json 2> $O/bench_$tag.err
+  nocpu="--no-cpu --no-pmc"; [ $tag = cfg2 ] && nocpu=""       # (cfg2: the cpu_baseline leg and the live counter passes included)
+  env $(envof $tag) timeout 900 python bench.py $(flags $tag) $(steps $tag) $nocpu --full > $O/bench_$tag.json 2> $O/bench_$tag.err
 done
-timeout 600 python bench.py --early-out --no-cpu --no-pmc > $O/bench_cfg2_early_out.json 2>/dev/null
-timeout 600 python bench.py --pairs 2000000 --no-cpu --no-pmc > $O/bench_cfg2_2m.json 2>/dev/null
+timeout 600 python bench.py --early-out --no-cpu --no-pmc --full > $O/bench_cfg2_early_out.json 2>/dev/null
+timeout 600 python bench.py --pairs 2000000 --no-cpu --no-pmc --full > $O/bench_cfg2_2m.json 2>/dev/null
 for tag in $TAGS; do
   [ $tag = cfg2_mutated ] && continue
   st=5; [ $tag = cfg3 ] && st=3

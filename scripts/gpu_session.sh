@@ -32,10 +32,10 @@ ragged)
       echo "$wl ragged, batch order: $(TA_TUNING=1 TA_NO_LENGTH_ORDER=1 run --workload $wl --dist ragged --steps 30 --warmup 5)"
     done
   done 2>&1 | tee $O/ragged.txt
-  python bench.py --workload cfg2 --dist ragged --steps 30 --no-cpu > $O/bench_cfg2_ragged.json 2>$O/bench_cfg2_ragged.err; cut -c1-600 $O/bench_cfg2_ragged.json; tail -3 $O/bench_cfg2_ragged.err ;;
+  python bench.py --workload cfg2 --dist ragged --steps 30 --no-cpu --full > $O/bench_cfg2_ragged.json 2>$O/bench_cfg2_ragged.err; cut -c1-600 $O/bench_cfg2_ragged.json; tail -3 $O/bench_cfg2_ragged.err ;;
 band)
   for wl in cfg2w cfg4w; do
-    python bench.py --workload $wl --steps 30 > $O/bench_$wl.json 2>$O/bench_$wl.err; cut -c1-400 $O/bench_$wl.json; tail -3 $O/bench_$wl.err
+    python bench.py --workload $wl --steps 30 --full > $O/bench_$wl.json 2>$O/bench_$wl.err; cut -c1-400 $O/bench_$wl.json; tail -3 $O/bench_$wl.err
     trace $wl --workload $wl --steps 10 --warmup 2
     python scripts/pmc_collect.py --out $O/${wl}_pmc.json --workload $wl --sets sq1,sq2,fetch,write,rd_b --steps 5 2>&1 | tail -2
   done ;;
@@ -118,7 +118,7 @@ benchlines)   # the bench lines again, now that profiles/<round>/ holds this bui
     case $tag in cfg2_mutated) fl="--workload cfg2 --dist mutated" ;; cfg2_ragged) fl="--workload cfg2 --dist ragged" ;; cfg2_dna) fl="--workload cfg2 --dist dna" ;; *) fl="--workload $tag" ;; esac
     case $tag in cfg3) st="--steps 3 --warmup 1" ;; cfg5) st="--steps 10 --warmup 2" ;; cfg2) st="" ;; *) st="--steps 50" ;; esac
     nocpu="--no-cpu"; [ $tag = cfg2 ] && nocpu=""
-    timeout 900 python bench.py $fl $st $nocpu > $O/lines/bench_$tag.json 2> $O/lines/bench_$tag.err
+    timeout 900 python bench.py $fl $st $nocpu --full > $O/lines/bench_$tag.json 2> $O/lines/bench_$tag.err
     cut -c1-150 $O/lines/bench_$tag.json; grep -h "not spliced" $O/lines/bench_$tag.err
   done
   python bench.py --gpus 1 --steps 20 --warmup 5 > $O/lines/bench_driver_command.json 2>/dev/null; cut -c1-200 $O/lines/bench_driver_command.json ;;

@@ -6,17 +6,19 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def _bench(*flags):
+def _bench(*flags, full=True):
+    """one bench.py line; full=True: with --full (the parity gates and the figures beside the headline these tests read)"""
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None); env.pop("RANK", None); env.pop("LOCAL_RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu", "--prewarm-ms", "20", *(() if "--pmc-live" in flags else ("--no-pmc",)),
-                        *[f for f in flags if f != "--pmc-live"]],
+                        *(("--full",) if full else ()), *[f for f in flags if f != "--pmc-live"]],
                        capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -64,7 +66,7 @@ def test_one_rank_under_the_launcher_equals_plain_run():
     env = dict(os.environ)
     for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(v, None)
-    flags = ["--steps", "20", "--warmup", "3", "--no-cpu", "--no-pmc", "--pairs", "500000", "--prewarm-ms", "300"]
+    flags = ["--steps", "20", "--warmup", "3", "--no-cpu", "--no-pmc", "--pairs", "500000", "--prewarm-ms", "300", "--full"]
     plain = _bench(*flags)                            # (argparse keeps the last --steps / --warmup)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29631", os.path.join(ROOT, "bench.py"), "--gpus", "1", *flags],
@@ -110,3 +112,16 @@ def test_default_line_carries_the_overlapped_figure_and_value_is():
     r = _bench("--pairs", "300000")
     assert r["value_is"] == "one GPU" and r["overlapped_passes"]["device_ms_per_pass"] > 0
     assert r["overlapped_passes"]["value"] > 0.9 * r["value"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing the run did not measure; --dump-outputs writes the timed pass's answers,
+    the same as those of a --full run of the same arguments (whose parity gate compares the batch's first 4,000 with the CPU oracle)."""
+    plain, full = tmp_path / "plain", tmp_path / "full"
+    r = _bench("--pairs", "20000", "--dist", "mutated", "--steps", "7", "--dump-outputs", str(plain), full=False)
+    assert r["steps"] == 7 and r["ms_per_step"] > 0 and r["value"] > 0 and r["kernel"]["kernel"] == 3
+    assert r["end_to_end_ms"] is None and r["overlapped_passes"] is None and r["parity_checked_units"] is None
+    _bench("--pairs", "20000", "--dist", "mutated", "--dump-outputs", str(full))
+    d = np.load(plain / "distances.npy")
+    assert d.dtype == np.float64 and d.shape == (20000,) and (d >= 0).sum() > 10000
+    assert np.array_equal(d, np.load(full / "distances.npy"))
