@@ -276,6 +276,45 @@ int ta_levenshtein_trace_batch(const ta_strings *a, const ta_strings *b, size_t 
 int ta_levenshtein_trace_batch_packed(const ta_strings *a, const ta_strings *b, size_t n, uint32_t k, const ta_edit_costs *costs,
                                       uint32_t *out_dev, uint32_t *packed_dev, uint32_t *n_edits_dev, size_t cap, void *stream);
 
+/* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
+ * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
+ * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of
+ * u32 items -- token ids, word ids -- resident in device memory.  Results follow the byte entries exactly (TA_NONE above k, the EditCosts
+ * checks, scripts edit for edit the scalar path's, src/levenshtein.rs:471-532, 561-606).
+ * Inside, a kernel codes every pair as two byte strings with  a[i] == b[j]  <=>  ca[i] == cb[j]  (the kernels only ever compare an item of
+ * a with an item of b), the byte entries run on the codes, and the rare pair whose shorter side is longer than 255 items and which holds
+ * more than 254 distinct common items is answered by the DP wide kernel over 32-bit items.
+ * Item i of sequence p is data[off[p] + i] (CSR, n+1 ELEMENT offsets) or data[p * stride + i] (off == NULL, `len` items each).  No read
+ * slack is required.  CSR: `len` = items `data` holds (an upper bound of off[n]; 0 = the library reads off[n]: one synchronisation), and
+ * max_len = 0 lets the library measure it (one synchronisation).  Scratch: the byte codes (one byte per item) and, for pairs whose
+ * shorter side exceeds 255 items, a hash table per wavefront. */
+typedef struct {
+    const uint32_t *data;    /* device */
+    const uint64_t *off;     /* device, n+1 element offsets, or NULL for the strided form */
+    uint64_t stride;         /* elements, strided form only */
+    uint64_t len;            /* strided: elements per sequence; CSR: elements `data` holds (0 = read off[n]) */
+    uint64_t max_len;        /* elements; CSR: 0 = let the library measure it */
+} ta_tokens;
+
+/* ta_levenshtein_k_batch over token sequences (levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:376; the batch contract of
+ * ta_levenshtein_k_batch).  Asynchronous and capturable (with max_len and len given) like its byte twin: the overflow pass reads the
+ * length of its list on the device. */
+int ta_levenshtein_k_batch_tokens(const ta_tokens *a, const ta_tokens *b, size_t n, uint32_t k,
+                                  const ta_edit_costs *costs, uint32_t *out_dev, void *stream);
+/* ta_levenshtein_exp_batch over token sequences (levenshtein_naive_with_opts<T>, src/levenshtein.rs:105-148): overflow pairs go straight
+ * to the unbounded pass (the distances do not depend on the schedule). */
+int ta_levenshtein_exp_batch_tokens(const ta_tokens *a, const ta_tokens *b, size_t n,
+                                    const ta_edit_costs *costs, uint32_t *out_dev, void *stream);
+/* ta_levenshtein_trace_batch over token sequences (levenshtein_naive_k_with_opts<T> with trace_on, src/levenshtein.rs:376, 561-606): the
+ * same buffers and `cap` cutting.  When a pair's shorter side can exceed 255 items the call reads the overflow count (ONE stream
+ * synchronisation: not capturable then) and traces the overflow pairs one by one (wide kernel + host walk) into the caller's buffers. */
+int ta_levenshtein_trace_batch_tokens(const ta_tokens *a, const ta_tokens *b, size_t n, uint32_t k, const ta_edit_costs *costs,
+                                      uint32_t *out_dev, ta_edit *edits_dev, uint32_t *n_edits_dev, size_t cap, void *stream);
+/* One pair from host memory (levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:376): *out = distance or TA_NONE; edits == NULL:
+ * distance only, else the run-length script (library-owned, ta_free) as ta_levenshtein_trace returns it. */
+int ta_levenshtein_tokens(const uint32_t *a, size_t a_len, const uint32_t *b, size_t b_len, uint32_t k,
+                          const ta_edit_costs *costs, uint32_t *out, ta_edit **edits, size_t *n_edits);
+
 /* N x hamming(a_i, b_i); out[i] = TA_NONE where the lengths differ (Rust: panic). */
 int ta_hamming_batch(const ta_strings *a, const ta_strings *b, size_t n, uint32_t *out_dev, void *stream);
 

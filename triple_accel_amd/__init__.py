@@ -192,6 +192,37 @@ def levenshtein_simd_k_with_opts(a, b, k, trace_on, costs):
     return None if d is None else (d, None)
 
 
+def _token_array(x):
+    import numpy as np
+    if isinstance(x, np.ndarray) and x.dtype == np.uint32:
+        return np.ascontiguousarray(x)
+    v = np.asarray(list(x) if not isinstance(x, np.ndarray) else x)
+    if v.size == 0:
+        return np.zeros(0, dtype=np.uint32)
+    if v.dtype == np.int32:
+        return np.ascontiguousarray(v.view(np.uint32))
+    v = v.astype(np.int64)
+    if v.min() < 0 or v.max() >= 1 << 32:
+        raise ValueError("token values must lie in [0, 2^32) (int32 tensors are taken as their u32 bit pattern)")
+    return np.ascontiguousarray(v.astype(np.uint32))
+
+
+def levenshtein_tokens(a, b, k=None, trace_on=False, costs=LEVENSHTEIN_COSTS):
+    """Edit distance of two sequences of 32-bit items (token ids): levenshtein_naive_k_with_opts<T> (src/levenshtein.rs:376) for
+    T = u32 -> None (distance above k) | (distance, None | [Edit]).  k = None: unbounded.  Sequences: lists of ints in [0, 2^32), or
+    int32 / uint32 / int64 arrays (int32 values are taken as their u32 bit pattern)."""
+    x, y = _token_array(a), _token_array(b)
+    kk = 0xFFFFFFFF if k is None else _k(k)
+    px, py = x.ctypes.data_as(_C.c_void_p), y.ctypes.data_as(_C.c_void_p)
+    cc = _costs(costs)._c()
+    if trace_on:
+        d, edits = _trace(_n.lib().ta_levenshtein_tokens, px, x.size, py, y.size, kk, _C.byref(cc))
+        return None if d is None else (d, edits)
+    out = _C.c_uint32()
+    _raise(_n.lib().ta_levenshtein_tokens(px, x.size, py, y.size, kk, _C.byref(cc), _C.byref(out), None, None))
+    return None if out.value == _n.NONE else (int(out.value), None)
+
+
 def levenshtein_simd_k(a, b, k):
     """src/levenshtein.rs:677"""
     a, b = _b(a), _b(b)

@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
     "ta_sharded_pairs_time_levenshtein_k", "ta_sharded_pairs_shards", "ta_sharded_pairs_free",
     "ta_sharded_haystack_upload", "ta_sharded_haystack_levenshtein_search", "ta_sharded_haystack_hamming_search",
     "ta_sharded_haystack_shards", "ta_sharded_haystack_free",
+    # token sequences (ta_tokens.hip)
+    "ta_levenshtein_k_batch_tokens", "ta_levenshtein_exp_batch_tokens", "ta_levenshtein_trace_batch_tokens", "ta_levenshtein_tokens",
 ]
 
 
@@ -58,6 +60,11 @@ class LaunchInfoC(C.Structure):
 
 class StringsC(C.Structure):
     _fields_ = [("blob", C.c_void_p), ("off", C.c_void_p), ("stride", C.c_uint64), ("len", C.c_uint64),
+                ("max_len", C.c_uint64)]
+
+
+class TokensC(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("off", C.c_void_p), ("stride", C.c_uint64), ("len", C.c_uint64),
                 ("max_len", C.c_uint64)]
 
 
@@ -168,6 +175,11 @@ def lib():
     sig("ta_sharded_haystack_hamming_search", i32, [vp, u8p, sz, u32, i32, mpp, szp])
     sig("ta_sharded_haystack_shards", i32, [vp, szp, szp])
     sig("ta_sharded_haystack_free", None, [vp])
+    tp = C.POINTER(TokensC)
+    sig("ta_levenshtein_k_batch_tokens", i32, [tp, tp, sz, u32, cp, C.c_void_p, C.c_void_p])
+    sig("ta_levenshtein_exp_batch_tokens", i32, [tp, tp, sz, cp, C.c_void_p, C.c_void_p])
+    sig("ta_levenshtein_trace_batch_tokens", i32, [tp, tp, sz, u32, cp, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    sig("ta_levenshtein_tokens", i32, [C.c_void_p, sz, C.c_void_p, sz, u32, cp, u32p, epp, szp])
     _lib = L
     return L
 

@@ -181,6 +181,112 @@ def packed_to_lists(packed, n_edits, allow_cut=False):
     return [[(_EDIT_NAMES[int(w) >> 29], int(w) & 0x1FFFFFFF) for w in p[i, cap - min(int(ne[i]), cap):]] for i in range(len(ne))]
 
 
+# ---------------------------------------------------------------- sequences of 32-bit items (token ids) resident in HBM
+def _token_values(t):
+    """int32 (taken as its u32 bit pattern) or int64 (checked to lie in [0, 2^32)) -> a contiguous int32 tensor of the same bits"""
+    if t.dtype == torch.int64:
+        if t.numel() and (int(t.min()) < 0 or int(t.max()) >= 1 << 32):
+            raise ValueError("token values must lie in [0, 2^32)")
+        t = torch.where(t >= 1 << 31, t - (1 << 32), t).to(torch.int32)
+    if t.dtype != torch.int32:
+        raise TypeError("token values: int32 or int64, got %s" % t.dtype)
+    return t.contiguous()
+
+
+class Tokens:
+    """A batch side of 32-bit item sequences in HBM (Strings for token ids): CSR (values + n+1 int64 element offsets) or a fixed
+    (n, len) tensor.  No read slack is needed."""
+
+    def __init__(self, values, off=None, length=0, max_len=0, n=None):
+        values = _token_values(values)
+        assert values.is_cuda
+        self.values, self.off, self.max_len = values, off, max_len
+        if off is not None:
+            assert off.dtype == torch.int64 and off.is_cuda and off.is_contiguous()
+            self.n, self.length, self.stride = off.numel() - 1, 0, 0
+        else:
+            self.n, self.length, self.stride = n, length, length
+
+    @classmethod
+    def from_csr(cls, values, off, max_len=0):
+        return cls(values, off, max_len=max_len)
+
+    @classmethod
+    def from_fixed(cls, array_2d, device="cuda"):
+        """(n, len) int32 / int64 tensor or array -> strided side"""
+        t = torch.as_tensor(array_2d)
+        n, length = t.shape
+        return cls(_token_values(t.to(device)).reshape(-1), None, length=length, n=n)
+
+    @classmethod
+    def from_list(cls, seqs, device="cuda"):
+        """a list of int sequences (values in [0, 2^32)) -> CSR side"""
+        import numpy as np
+        lens = np.fromiter((len(s) for s in seqs), dtype=np.int64, count=len(seqs))
+        off = np.zeros(len(seqs) + 1, dtype=np.int64)
+        np.cumsum(lens, out=off[1:])
+        vals = np.zeros(int(off[-1]), dtype=np.int64)
+        if off[-1]:
+            vals[:] = np.concatenate([np.asarray(s, dtype=np.int64).reshape(-1) for s in seqs if len(s)])
+        return cls(torch.from_numpy(vals).to(device), torch.from_numpy(off).to(device), max_len=int(lens.max()) if len(seqs) else 0)
+
+    def longest(self):
+        if self.off is None:
+            return int(self.length)
+        if not self.max_len and self.n > 0:
+            self.max_len = int((self.off[1:] - self.off[:-1]).max().item())
+        return int(self.max_len)
+
+    def _ref(self):
+        c = self.__dict__.get("_cview")
+        if c is None:
+            # CSR: `len` carries the items the values hold (the bound of off[n]: the library then needs no synchronisation for it)
+            c = self._cview = _n.TokensC(self.values.data_ptr(), 0 if self.off is None else self.off.data_ptr(), self.stride,
+                                         self.length if self.off is None else self.values.numel(), self.max_len)
+            self._cref = _C.byref(c)
+        return self._cref
+
+
+def levenshtein_k_batch_tokens(a: Tokens, b: Tokens, k, costs=LEVENSHTEIN_COSTS, out=None):
+    """levenshtein_k_batch over token sequences: out[i] = the distance of pair i if <= k, else -1 (int32)."""
+    assert a.n == b.n
+    a.longest(), b.longest()
+    out = _out(a.n, a.values.device) if out is None else out
+    cc = _costs(costs)._c()
+    rc = _n.lib().ta_levenshtein_k_batch_tokens(a._ref(), b._ref(), a.n, k, _C.byref(cc), out.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return out
+
+
+def levenshtein_exp_batch_tokens(a: Tokens, b: Tokens, costs=LEVENSHTEIN_COSTS, out=None):
+    """levenshtein_exp_batch over token sequences (the distance of every pair)"""
+    assert a.n == b.n
+    a.longest(), b.longest()
+    out = _out(a.n, a.values.device) if out is None else out
+    cc = _costs(costs)._c()
+    _raise(_n.lib().ta_levenshtein_exp_batch_tokens(a._ref(), b._ref(), a.n, _C.byref(cc), out.data_ptr(), _stream()))
+    return out
+
+
+def levenshtein_trace_batch_tokens(a: Tokens, b: Tokens, k, costs=LEVENSHTEIN_COSTS, cap=None, out=None, edits=None, n_edits=None):
+    """levenshtein_trace_batch over token sequences: -> (out, edits, n_edits) as levenshtein_trace_batch returns them."""
+    assert a.n == b.n
+    n, dev = a.n, a.values.device
+    if cap is None:
+        cap = min(2 * int(k) + 1, 2 * max(a.longest(), b.longest(), 1) + 1)
+    a.longest(), b.longest()
+    out = _out(n, dev) if out is None else out
+    edits = torch.empty((n, cap, 2), dtype=torch.int64, device=dev) if edits is None else edits
+    n_edits = torch.empty(n, dtype=torch.int32, device=dev) if n_edits is None else n_edits
+    cc = _costs(costs)._c()
+    rc = _n.lib().ta_levenshtein_trace_batch_tokens(a._ref(), b._ref(), n, k, _C.byref(cc), out.data_ptr(), edits.data_ptr(),
+                                                    n_edits.data_ptr(), cap, _stream())
+    if rc:
+        _raise(rc)
+    return out, edits, n_edits
+
+
 def hamming_batch(a: Strings, b: Strings, out=None):
     assert a.n == b.n
     out = _out(a.n, a.blob.device) if out is None else out

@@ -35,21 +35,29 @@ __device__ __forceinline__ uint32_t dpp_from_lower(uint32_t x, uint32_t fill) {
 }
 __device__ __forceinline__ uint32_t umin_(uint32_t a, uint32_t b) { return a < b ? a : b; }
 
-__device__ __forceinline__ void wide_str(const StrView &s, uint32_t i, const uint8_t *&p, uint32_t &len) {
+// SYM = uint8_t: a byte string; SYM = uint32_t: a token string (the view's blob holds u32 items, offsets and stride count items)
+template <typename SYM>
+__device__ __forceinline__ void wide_str(const StrView &s, uint32_t i, const SYM *&p, uint32_t &len) {
+    const SYM *base = (const SYM *)s.blob;
     if (s.off) {
         uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
+        p = base + o0;
         len = (uint32_t)(o1 - o0);
     } else {
-        p = s.blob + (uint64_t)i * s.stride;
+        p = base + (uint64_t)i * s.stride;
         len = (uint32_t)s.len;
     }
 }
 
 // TRACE (one pair, trace_on = true): 2-bit argmin codes with the scalar tie order (src/levenshtein.rs:493-532), 32 rows =
 // 2 dwords per lane per column, at P.trace[((stripe * P.trace_cols + j) * 64 + lane) * 2 + word]
-template <bool AFFINE, bool TRANS, bool TRACE = false>
+// SYM: the item type.  uint8_t: rows packed four per VGPR, the byte test by v_perm / v_dot4 (the byte kernels' form).  uint32_t: the
+// token route of the batch entries (ta_tokens.hip: pairs with more distinct common items than a byte holds) -- rows unpacked, one VGPR
+// per row item, the column item handed down the lanes as a full dword; the recurrence is the same code.
+template <bool AFFINE, bool TRANS, bool TRACE = false, typename SYM = uint8_t>
 __global__ __launch_bounds__(64) void lev_wide_kernel(LevParams P, WideScratch S) {
+    constexpr bool U8 = sizeof(SYM) == 1;
+    constexpr int NA = U8 ? WR / 4 : WR;     // VGPRs of row items per lane
     const uint32_t t = threadIdx.x;   // lane
     const uint32_t gc = P.gc, sg = P.sg, sgc = P.sg + P.gc, mc = P.mc, tc = P.tc, u = P.u;
     uint32_t *line_base = S.buf + (uint64_t)blockIdx.x * (6 * S.line);
@@ -58,10 +66,10 @@ __global__ __launch_bounds__(64) void lev_wide_kernel(LevParams P, WideScratch S
     const uint32_t n_pairs = P.n_dev ? *P.n_dev : P.n;   // (a list whose length only the device knows: the rounds of ta_levenshtein_exp_batch)
     for (uint32_t slot = blockIdx.x; slot < n_pairs; slot += gridDim.x) {
         const uint32_t pair = P.subset ? P.subset[slot] : slot;
-        const uint8_t *ap, *bp;
+        const SYM *ap, *bp;
         uint32_t n, m;
-        wide_str(P.a, pair, ap, n);
-        wide_str(P.b, pair, bp, m);
+        wide_str<SYM>(P.a, pair, ap, n);
+        wide_str<SYM>(P.b, pair, bp, m);
         const uint32_t diff = n > m ? n - m : m - n;
         if (diff > u) { if (t == 0) P.out[pair] = 0xFFFFFFFFu; continue; }             // :426-428
         if (n == 0 || m == 0) {                                                          // one gap run or ("", "")
@@ -96,24 +104,37 @@ __global__ __launch_bounds__(64) void lev_wide_kernel(LevParams P, WideScratch S
                 return (j >= plo && j <= phi) ? rd[2 * S.line + j] : WINF;
             };
 
-            // this lane's rows: chars packed 4 per VGPR (byte r&3 of word r>>2 = char of row row0 + 1 + r)
+            // this lane's rows: chars packed 4 per VGPR (byte r&3 of word r>>2 = char of row row0 + 1 + r); tokens one per VGPR
             const uint32_t row0 = i0 + t * WR;           // the row just above the lane's first row
-            uint32_t A4[WR / 4], AU4[TRANS ? WR / 4 : 1];
+            uint32_t A4[NA], AU4[TRANS ? NA : 1];
+            if constexpr (U8) {
 #pragma unroll
-            for (int w = 0; w < WR / 4; w++) {
-                uint32_t v = 0;
+                for (int w = 0; w < WR / 4; w++) {
+                    uint32_t v = 0;
 #pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    uint32_t ci = row0 + w * 4 + b;      // 0-based index into a
-                    v |= ((ci < n) ? (uint32_t)ap[ci] : 0u) << (8 * b);
+                    for (int b = 0; b < 4; b++) {
+                        uint32_t ci = row0 + w * 4 + b;  // 0-based index into a
+                        v |= ((ci < n) ? (uint32_t)ap[ci] : 0u) << (8 * b);
+                    }
+                    A4[w] = v;
                 }
-                A4[w] = v;
-            }
-            if (TRANS) {                                 // AU4: char of the row above each row
-                uint32_t above = (row0 >= 1 && row0 - 1 < n) ? (uint32_t)ap[row0 - 1] : 0u;
+                if (TRANS) {                             // AU4: char of the row above each row
+                    uint32_t above = (row0 >= 1 && row0 - 1 < n) ? (uint32_t)ap[row0 - 1] : 0u;
 #pragma unroll
-                for (int w = 0; w < WR / 4; w++)
-                    AU4[w] = __builtin_amdgcn_alignbyte(A4[w], w ? A4[w - 1] : (above << 24), 3);
+                    for (int w = 0; w < WR / 4; w++)
+                        AU4[w] = __builtin_amdgcn_alignbyte(A4[w], w ? A4[w - 1] : (above << 24), 3);
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < WR; r++) {
+                    const uint32_t ci = row0 + r;
+                    A4[r] = (ci < n) ? (uint32_t)ap[ci] : 0u;
+                }
+                if (TRANS) {                             // AU4: token of the row above each row
+                    const uint32_t above = (row0 >= 1 && row0 - 1 < n) ? (uint32_t)ap[row0 - 1] : 0u;
+#pragma unroll
+                    for (int r = 0; r < WR; r++) AU4[r] = r ? A4[r - 1] : above;
+                }
             }
 
             // state of the column left of the stripe's first column (jlo - 1)
@@ -176,14 +197,22 @@ __global__ __launch_bounds__(64) void lev_wide_kernel(LevParams P, WideScratch S
                     if (TRANS) { up2_prev2 = up2_prev; up2_prev = up2_dp; up2_dp = in_dp2; }
                     const uint32_t bprev = bch;
                     bch = in_b;
-                    const uint32_t B4 = bch * 0x01010101u;
-                    uint32_t F4[WR / 4], Z4[TRANS ? WR / 4 : 1];
+                    uint32_t F4[NA], Z4[TRANS ? NA : 1];
+                    if constexpr (U8) {
+                        const uint32_t B4 = bch * 0x01010101u;
 #pragma unroll
-                    for (int w = 0; w < WR / 4; w++) {
-                        // 1 per mismatching row: the XOR plus 0x0C is 12 exactly where the bytes agree, and v_perm_b32 with all-ones
-                        // sources maps byte value 12 to 0x00 and every other one to 0xFF (wave.h, W::ne12)
-                        F4[w] = __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, A4[w] ^ B4 ^ 0x0C0C0C0Cu) & 0x01010101u;
-                        if (TRANS) Z4[w] = (A4[w] ^ (bprev * 0x01010101u)) | (AU4[w] ^ B4);   // 0: a[i]==b[j-1] && a[i-1]==b[j]
+                        for (int w = 0; w < WR / 4; w++) {
+                            // 1 per mismatching row: the XOR plus 0x0C is 12 exactly where the bytes agree, and v_perm_b32 with all-ones
+                            // sources maps byte value 12 to 0x00 and every other one to 0xFF (wave.h, W::ne12)
+                            F4[w] = __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, A4[w] ^ B4 ^ 0x0C0C0C0Cu) & 0x01010101u;
+                            if (TRANS) Z4[w] = (A4[w] ^ (bprev * 0x01010101u)) | (AU4[w] ^ B4);   // 0: a[i]==b[j-1] && a[i-1]==b[j]
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < WR; r++) {
+                            F4[r] = (A4[r] != bch) ? mc : 0u;                                // the substitution's price of row r
+                            if (TRANS) Z4[r] = (A4[r] == bprev && AU4[r] == bch) ? 0u : 1u;  // 0: a[i]==b[j-1] && a[i-1]==b[j]
+                        }
                     }
                     uint32_t diag = up_dp_prev;          // dp(row0, j-1)
                     uint32_t gb = in_gb;                 // B(row0 + 1, j)
@@ -193,7 +222,9 @@ __global__ __launch_bounds__(64) void lev_wide_kernel(LevParams P, WideScratch S
                     uint32_t codes[2] = {0u, 0u};
 #pragma unroll
                     for (int r = 0; r < WR; r++) {
-                        const uint32_t sub = __builtin_amdgcn_udot4(F4[r >> 2], mc << (8 * (r & 3)), diag, false);   // :471-475
+                        uint32_t sub;
+                        if constexpr (U8) sub = __builtin_amdgcn_udot4(F4[r >> 2], mc << (8 * (r & 3)), diag, false);   // :471-475
+                        else sub = diag + F4[r];
                         const uint32_t oldH = H[r];
                         const uint32_t ga = GA[r];
                         v_above = v;
@@ -203,7 +234,9 @@ __global__ __launch_bounds__(64) void lev_wide_kernel(LevParams P, WideScratch S
                         if (TRANS) {
                             const uint32_t td = p2a;                                     // dp(i-2, j-2)
                             p2a = p2b; p2b = P2[r]; P2[r] = oldH;
-                            const bool tz = ((Z4[r >> 2] >> (8 * (r & 3))) & 0xffu) == 0u;
+                            bool tz;
+                            if constexpr (U8) tz = ((Z4[r >> 2] >> (8 * (r & 3))) & 0xffu) == 0u;
+                            else tz = Z4[r] == 0u;
                             const uint32_t tv = td + tc;
                             if (TRACE) code = (tz && tv <= v) ? 3u : code;               // transposition wins ties (<=)
                             v = (tz && tv < v) ? tv : v;                                 // :517-532
@@ -267,7 +300,7 @@ hipError_t lev_wide_launch(const LevParams &P, bool trans, hipStream_t s, uint32
     if (sc.ensure((size_t)grid * 6 * S.line * sizeof(uint32_t)) != TA_OK) return hipErrorOutOfMemory;
     S.buf = (uint32_t *)sc.dev;
     const bool affine = P.sg > 0;
-    set_last_kernel_name("lev_wide_kernel<%s, %s, false>", affine ? "true" : "false", trans ? "true" : "false");
+    set_last_kernel_name("lev_wide_kernel<%s, %s, false, unsigned char>", affine ? "true" : "false", trans ? "true" : "false");
     if (affine && trans) hipLaunchKernelGGL((lev_wide_kernel<true, true>), dim3(grid), dim3(64), 0, s, P, S);
     else if (affine) hipLaunchKernelGGL((lev_wide_kernel<true, false>), dim3(grid), dim3(64), 0, s, P, S);
     else if (trans) hipLaunchKernelGGL((lev_wide_kernel<false, true>), dim3(grid), dim3(64), 0, s, P, S);
@@ -287,6 +320,36 @@ hipError_t lev_wide_trace_launch(const LevParams &P, bool trans, hipStream_t s) 
     else if (affine) hipLaunchKernelGGL((lev_wide_kernel<true, false, true>), dim3(1), dim3(64), 0, s, P, S);
     else if (trans) hipLaunchKernelGGL((lev_wide_kernel<false, true, true>), dim3(1), dim3(64), 0, s, P, S);
     else hipLaunchKernelGGL((lev_wide_kernel<false, false, true>), dim3(1), dim3(64), 0, s, P, S);
+    return hipGetLastError();
+}
+
+// The token form over the pairs of P.subset (the compaction's overflow list, its length in *P.n_dev -- read on the device; P.n bounds the
+// grid) or over P.n pairs: the same sweep with 32-bit items.  trace: one pair, P.trace / P.trace_cols set (as lev_wide_trace_launch).
+hipError_t lev_wide_u32_launch(const LevParams &P, bool trans, bool trace, hipStream_t s) {
+    uint32_t grid = trace ? 1u : P.n;
+    int dev = 0, cus = 256;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    const uint32_t resident = (uint32_t)cus * 4u * 4u;
+    if (grid > resident) grid = resident;
+    if (grid == 0) return hipSuccess;
+    WideScratch S;
+    S.line = (uint64_t)P.lds_per_wave;
+    Scratch &sc = tls_scratch(6);
+    if (sc.ensure((size_t)grid * 6 * S.line * sizeof(uint32_t)) != TA_OK) return hipErrorOutOfMemory;
+    S.buf = (uint32_t *)sc.dev;
+    const bool affine = P.sg > 0;
+#define TA_WIDE_U32(A, T)                                                                                                  \
+    do {                                                                                                                   \
+        if (trace) hipLaunchKernelGGL((lev_wide_kernel<A, T, true, uint32_t>), dim3(grid), dim3(64), 0, s, P, S);               \
+        else hipLaunchKernelGGL((lev_wide_kernel<A, T, false, uint32_t>), dim3(grid), dim3(64), 0, s, P, S);                    \
+    } while (0)
+    if (affine && trans) TA_WIDE_U32(true, true);
+    else if (affine) TA_WIDE_U32(true, false);
+    else if (trans) TA_WIDE_U32(false, true);
+    else TA_WIDE_U32(false, false);
+#undef TA_WIDE_U32
     return hipGetLastError();
 }
 

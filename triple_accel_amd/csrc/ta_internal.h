@@ -34,7 +34,7 @@ struct Scratch {
     void release();
     ~Scratch();
 };
-constexpr int TA_SCRATCH_SLOTS = 18;
+constexpr int TA_SCRATCH_SLOTS = 23;   // 18..22: the token entries (ta_tokens.hip)
 constexpr int TA_SLOT_SEARCH_HAY = 17;        // the host search entries' haystack staging: nothing else writes it (ta_levenshtein_search_resume relies on that)
 Scratch &tls_scratch(int which);
 
@@ -101,6 +101,10 @@ hipError_t lev_wide_trace_launch(const LevParams &P, bool trans, hipStream_t s);
 hipError_t lev_widebits_trace_launch(const LevParams &P, bool trans, hipStream_t s);
 hipError_t lev_wide_launch(const LevParams &P, bool trans, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out,
                            uint32_t *threads_out, uint32_t *dpt_out);
+// the DP wide kernel over 32-bit items (token batches' overflow pairs): P.subset / P.n_dev as a list, or P.n pairs; trace: one pair
+hipError_t lev_wide_u32_launch(const LevParams &P, bool trans, bool trace, hipStream_t s);
+struct SymCompactParams;
+hipError_t sym_compact_launch(const SymCompactParams &P, uint32_t waves, hipStream_t s);
 hipError_t hamming_batch_launch(const StrView &a, const StrView &b, uint32_t n, uint32_t *out, hipStream_t s);
 hipError_t strings_maxlen_launch(const StrView &s, uint32_t n, uint32_t *out_max /*device, pre-zeroed*/, hipStream_t st);
 hipError_t compact_none_launch(const uint32_t *out, const uint32_t *subset_in, uint32_t n_in, const uint32_t *n_in_dev /*optional: the list's length on the device*/,
