@@ -276,6 +276,29 @@ int ta_levenshtein_trace_batch(const ta_strings *a, const ta_strings *b, size_t 
 int ta_levenshtein_trace_batch_packed(const ta_strings *a, const ta_strings *b, size_t n, uint32_t k, const ta_edit_costs *costs,
                                       uint32_t *out_dev, uint32_t *packed_dev, uint32_t *n_edits_dev, size_t cap, void *stream);
 
+/* N x ta_levenshtein_search_simd_with_opts(needle_i, haystack_i, k, search_type, costs, anchored) on device-resident data (no reference
+ * analogue: the reference searches one haystack per call, src/levenshtein.rs:1911-1966).  Pair i's result is exactly that call's -- the
+ * end == 0 match (:1693-1706), the empty-needle answers (:1919-1963), the Best fold (:1812-1835), quirk Q2 -- with positions relative to
+ * haystack i: counts_dev[i] = its length, matches_dev[i * cap .. i * cap + min(counts_dev[i], cap)) = its first `cap` matches in the
+ * reference's order (increasing end; pad_ = 0).  cap = 0: counts only ("which reads contain the adapter").  The cut at `cap` is
+ * ta_levenshtein_trace_batch's convention.  `needles` may be the strided form with stride = 0: ONE needle blob[0 .. len) shared by every
+ * pair (an adapter, a primer) -- the only form that takes the scan route below; per-pair needles (CSR or strided) are fully supported.
+ * Both sides follow the TA_BLOB_SLACK rule.  One haystack is ONE lane's work: the entry is meant for many short-to-medium haystacks (reads,
+ * records); a long haystack belongs on ta_levenshtein_search_dev, which spreads one haystack over the whole device.
+ * Routes: the exact recurrence over each whole haystack, one lane per pair, longest haystacks first; for a shared needle
+ * of up to 64 bytes, unanchored, a bit-parallel unit-cost scan first finds each haystack's span of candidate ends (a superset filter
+ * under any EditCosts) and the exact recurrence runs on those spans only.
+ * Errors, all before any device work: TA_ERR_BAD_COSTS when EditCosts::new or check_search fails (:1965) -- decided for the whole batch,
+ * even when every needle is empty (the single call does not check an empty needle's costs against check_search); TA_ERR_ARG for null
+ * pointers with n > 0, a search_type other than 0 / 1, n * cap overflowing, or a needle over 65,535 bytes (the host search forms'
+ * limit); TA_ERR_UNSUPPORTED for a haystack of 2^32 bytes or more.  No device: TA_ERR_HIP.
+ * The call enqueues its work on `stream` and returns without synchronising.  With every length bound known (strided sides, CSR max_len
+ * given on both) it is capturable, like the other batches: no host round trip between kernels, the candidate list's length is read on
+ * the device; a CSR side with max_len = 0 costs one synchronisation to measure it. */
+int ta_levenshtein_search_batch(const ta_strings *needles, const ta_strings *haystacks, size_t n,
+                                uint32_t k, int search_type, const ta_edit_costs *costs, int anchored,
+                                ta_match *matches_dev, uint32_t *counts_dev, size_t cap, void *stream);
+
 /* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
  * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
  * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of

@@ -6,7 +6,7 @@ import ctypes as _C
 import torch
 
 from . import _native as _n
-from . import EditCosts, LEVENSHTEIN_COSTS, _costs, _raise
+from . import EditCosts, LEVENSHTEIN_COSTS, SearchType, _costs, _raise
 
 SLACK = 16
 
@@ -50,6 +50,16 @@ class Strings:
         blob = torch.zeros(n * length + SLACK, dtype=torch.uint8, device=device)
         blob[: n * length] = t.reshape(-1).to(device)
         return cls(blob, None, stride=length, length=length, n=n)
+
+    @classmethod
+    def shared(cls, needle, n, device="cuda"):
+        """ONE needle for a batch of n pairs: the strided form with stride 0 (levenshtein_search_batch's shared needle -- an adapter,
+        a primer -- the only needle form its scan route takes)"""
+        needle = bytes(needle)
+        blob = torch.zeros(len(needle) + SLACK, dtype=torch.uint8)
+        if needle:
+            blob[:len(needle)] = torch.frombuffer(bytearray(needle), dtype=torch.uint8)
+        return cls(blob.to(device), None, stride=0, length=len(needle), n=n)
 
     def longest(self):
         """an upper bound on the length of any string of the side: `length` (strided), `max_len` when the caller gave it, else
@@ -406,3 +416,40 @@ def haystack_tensor(data, device="cuda"):
     t = torch.zeros(arr.size + SLACK, dtype=torch.uint8, device=device)
     t[: arr.size] = torch.from_numpy(np.ascontiguousarray(arr)).to(device)
     return t, arr.size
+
+
+def levenshtein_search_batch(needles: Strings, haystacks: Strings, k, search_type=SearchType.Best, costs=LEVENSHTEIN_COSTS, anchored=False, cap=None,
+                             matches=None, counts=None):
+    """levenshtein_search_simd_with_opts(needle_i, haystack_i, k, search_type, costs, anchored) for every pair, on the device:
+    -> (matches, counts).  counts[i] (int32) = the length of pair i's result; matches[i, :min(counts[i], cap)] = its first `cap`
+    matches as int64 (start, end, k) rows, positions relative to haystack i, in increasing end.  cap = 0: counts only.
+    needles may be Strings.shared(needle, n): one needle for every pair.  Default cap: 8 (search_type Best) or 64 (All)."""
+    st = search_type
+    n, dev = haystacks.n, haystacks.blob.device
+    assert needles.n == n
+    if cap is None:
+        cap = 8 if st == SearchType.Best else 64
+    matches = torch.empty((n, cap, 3), dtype=torch.int64, device=dev) if matches is None else matches
+    counts = torch.empty(n, dtype=torch.int32, device=dev) if counts is None else counts
+    assert matches.dtype == torch.int64 and matches.is_contiguous() and matches.numel() >= n * cap * 3
+    assert counts.dtype == torch.int32 and counts.numel() >= n
+    cc = _costs(costs)._c()
+    rc = _n.lib().ta_levenshtein_search_batch(needles._ref(), haystacks._ref(), n, int(k), int(st), _C.byref(cc), int(bool(anchored)),
+                                              matches.data_ptr() if cap else None, counts.data_ptr(), cap, _stream())
+    if rc:
+        _raise(rc)
+    return matches, counts
+
+
+def matches_to_lists(matches, counts, allow_cut=False):
+    """the device result of levenshtein_search_batch as Python lists of triple_accel_amd.Match per pair (host copy).  A result longer
+    than the `cap` rows of its pair was cut on the device (counts says how long it is): that is an error here, not a silently shorter
+    list, unless the caller asks for the cut lists (allow_cut)."""
+    from . import Match
+    m, c = matches.cpu().numpy(), counts.cpu().numpy().astype("int64")
+    cap = m.shape[1]
+    cut = [i for i in range(len(c)) if int(c[i]) > cap]
+    if cut and not allow_cut:
+        raise ValueError("levenshtein_search_batch: %d result(s) longer than cap = %d matches (first: pair %d with %d); pass a larger cap"
+                         % (len(cut), cap, cut[0], int(c[cut[0]])))
+    return [[Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF) for r in m[i, :min(int(c[i]), cap)]] for i in range(len(c))]

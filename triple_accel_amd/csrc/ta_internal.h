@@ -34,7 +34,7 @@ struct Scratch {
     void release();
     ~Scratch();
 };
-constexpr int TA_SCRATCH_SLOTS = 23;   // 18..22: the token entries (ta_tokens.hip)
+constexpr int TA_SCRATCH_SLOTS = 30;   // 18..22: the token entries (ta_tokens.hip); 23..29: the search batch (ta_search_batch.hip)
 constexpr int TA_SLOT_SEARCH_HAY = 17;        // the host search entries' haystack staging: nothing else writes it (ta_levenshtein_search_resume relies on that)
 Scratch &tls_scratch(int which);
 
@@ -198,6 +198,26 @@ hipError_t lev_search_wave_launch(const SearchParams &P, bool trans, bool best, 
                                   hipStream_t s);
 hipError_t search_report_copy_launch(const unsigned long long *count, const uint32_t *nul_flag, const ta_match *hits, uint64_t cap, uint8_t *box, hipStream_t s);
 hipError_t hamming_search_launch(const SearchParams &P, hipStream_t s, uint32_t *nul_flag = nullptr, bool *nul_done = nullptr);
+
+// ta_levenshtein_search_batch (lev_search_batch.hip): one lane per (needle, haystack) pair
+struct SearchBatchParams {
+    StrView nd, hs;               // needles (the strided form with stride 0: one shared needle), haystacks
+    ta_match *matches;            // device: cap slots per pair
+    uint32_t *counts;             // device: the length of each pair's result
+    uint64_t cap;
+    uint32_t n;                   // pairs (the grid's bound)
+    const uint32_t *list;         // the pairs in the order they are taken, or nullptr: 0..n
+    const uint32_t *n_list;       // device: the list's length (Route S's candidates), or nullptr: n
+    uint32_t *span;               // Route S: [2 pair], [2 pair + 1] = first and last candidate end; nullptr: Route E
+    uint32_t *cand_list, *cand_count;   // Route S scan: the pairs with a candidate, their number (pre-zeroed)
+    uint32_t k, mc, gc, sg, tc, anchored, best;
+    uint32_t kf, halo;            // Route S: the scan's threshold, the exact pass's left context
+    uint32_t max_needle;          // bound on every needle's length (the packed form: the needle's length)
+    uint32_t *col;                // memory form: 6 (max_needle + 1) u32 per resident lane
+};
+hipError_t search_batch_maxlen_launch(const StrView &nd, const StrView &hs, uint32_t n, unsigned long long *max /*2, pre-zeroed*/, hipStream_t st);
+hipError_t search_batch_exact_launch(const SearchBatchParams &P, bool trans, bool packed, uint32_t mem_lanes, hipStream_t st);
+hipError_t search_batch_scan_launch(const SearchBatchParams &P, bool trans, hipStream_t st);
 
 // ta_multi.hip: the device set (one worker thread per entry).  multi_search_shards / multi_pair_shards: over how many of them a host
 // haystack / a host batch of that size is spread (1: the calling thread's own device path).  The search forms return the All-mode hits
