@@ -299,6 +299,30 @@ int ta_levenshtein_search_batch(const ta_strings *needles, const ta_strings *hay
                                 uint32_t k, int search_type, const ta_edit_costs *costs, int anchored,
                                 ta_match *matches_dev, uint32_t *counts_dev, size_t cap, void *stream);
 
+/* N x ta_hamming_search_simd_with_opts(needle_i, haystack_i, k, search_type) on device-resident data (no reference analogue: the reference
+ * searches one haystack per call, src/hamming.rs:454-475, scalar text :96-146).  Pair i's result is exactly that call's, in the layout of
+ * ta_levenshtein_search_batch: counts_dev[i] = its length, matches_dev[i * cap .. i * cap + min(counts_dev[i], cap)) = its first `cap`
+ * matches in increasing start (end = start + needle_len, k = the mismatch count, pad_ = 0), positions relative to haystack i.  cap = 0:
+ * counts only, matches_dev may be NULL.  The reference's checks keep their order per pair: needle_len > haystack_len, then needle_len == 0,
+ * give an empty result (:455-461); only then a haystack that holds a 0x00 byte gets counts_dev[i] = TA_NONE and no matches (its slots are
+ * not meaningful) where the single call returns TA_ERR_NULL_BYTE -- the other pairs are unaffected and the call returns TA_OK.  A NUL byte
+ * in a needle, or in a haystack shorter than its needle, is not an error.  Best is the scalar routine's rule (:105-142): the windows at
+ * the smallest mismatch count <= k, no overlap fold -- ta_search_fold_best(.., overlap_fold = 0) -- and counts_dev[i] is their number
+ * whatever `cap` is.  All-mode k >= needle_len reports every offset.  `needles` may be the strided form with stride = 0: ONE needle shared
+ * by every pair (a barcode, a primer); per-pair needles (CSR or strided) of up to 65,535 bytes are fully supported.  Both sides follow the
+ * TA_BLOB_SLACK rule.  One haystack is ONE lane's work; a long haystack belongs on ta_hamming_search_dev.
+ * Routes: a SWAR window compare for every input (needle in registers up to 64 bytes, CSR batches of >= 4096 pairs longest
+ * haystack first); bit-sliced mismatch counters for a shared needle of up to 32 bytes with 4 k <= needle_len.
+ * Errors, all before any device work: TA_ERR_ARG for NULL needles / haystacks, with n > 0 a NULL blob, NULL counts_dev or cap > 0 with NULL
+ * matches_dev, a search_type other than 0 / 1, n * cap * sizeof(ta_match) overflowing, or a needle over 65,535 bytes; TA_ERR_UNSUPPORTED
+ * for a haystack of 2^32 bytes or more.  No device: TA_ERR_HIP.  n == 0: TA_OK.
+ * The call enqueues its work on `stream` and returns without synchronising.  With every length bound known (strided sides, CSR max_len
+ * given on both) it is capturable under the rule above (run once outside the capture first); a CSR side with max_len = 0 costs one
+ * synchronisation to measure it.  ta_last_kernel_name names the route taken. */
+int ta_hamming_search_batch(const ta_strings *needles, const ta_strings *haystacks, size_t n,
+                            uint32_t k, int search_type,
+                            ta_match *matches_dev, uint32_t *counts_dev, size_t cap, void *stream);
+
 /* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
  * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
  * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of

@@ -350,6 +350,38 @@ def levenshtein_search_many(needle_or_needles, haystacks, k=None, search_type=Se
     return B.matches_to_lists(m, c)
 
 
+def hamming_search_many(needle_or_needles, haystacks, k=None, search_type=SearchType.Best):
+    """[list(hamming_search_simd_with_opts(needle_i, haystack_i, k, search_type)) for every haystack] in ONE device batch
+    (ta_hamming_search_batch): one needle (bytes) for every haystack, or a list of needles, one per haystack.  k = None: the
+    hamming_search default ceil(len(needle) / 2) of a shared needle (src/hamming.rs:423).  Raises PanicError where a single call would
+    (a NUL byte in a haystack that is not shorter than its non-empty needle).  The haystacks are uploaded; a result longer than the
+    first call's room is answered by one more call with room for the longest."""
+    import torch
+    from . import batch as B
+    hays = [_b(h) for h in haystacks]
+    n = len(hays)
+    if isinstance(needle_or_needles, (list, tuple)):
+        needles = [_b(x) for x in needle_or_needles]
+        if len(needles) != n:
+            raise ValueError("hamming_search_many: %d needles for %d haystacks" % (len(needles), n))
+        if k is None:
+            raise ValueError("hamming_search_many: k is required with per-haystack needles")
+        side = B.Strings.from_list(needles)
+    else:
+        needle = _b(needle_or_needles)
+        if k is None:
+            k = (len(needle) + 1) // 2
+        side = B.Strings.shared(needle, n)
+    hs = B.Strings.from_list(hays)
+    k = _k(k)
+    m, c = B.hamming_search_batch(side, hs, k, search_type)
+    longest = int(c.max().item()) if n else 0
+    if longest > m.shape[1]:
+        m, c = B.hamming_search_batch(side, hs, k, search_type, cap=longest)
+    torch.cuda.current_stream().synchronize()
+    return B.matches_to_lists(m, c)
+
+
 def levenshtein_select(a_len, b_len, k, costs=LEVENSHTEIN_COSTS):
     """The dispatcher arithmetic (src/levenshtein.rs:731-791): (max_k, unit_k, cell_bits, ref_lanes)."""
     s = _n.LevSelectC()

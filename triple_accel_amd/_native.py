@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     # token sequences (ta_tokens.hip)
     "ta_levenshtein_k_batch_tokens", "ta_levenshtein_exp_batch_tokens", "ta_levenshtein_trace_batch_tokens", "ta_levenshtein_tokens",
     # search over a batch of (needle, haystack) pairs (ta_search_batch.hip)
-    "ta_levenshtein_search_batch",
+    "ta_levenshtein_search_batch", "ta_hamming_search_batch",
 ]
 
 
@@ -183,6 +183,7 @@ def lib():
     sig("ta_levenshtein_trace_batch_tokens", i32, [tp, tp, sz, u32, cp, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     sig("ta_levenshtein_tokens", i32, [C.c_void_p, sz, C.c_void_p, sz, u32, cp, u32p, epp, szp])
     sig("ta_levenshtein_search_batch", i32, [sp, sp, sz, u32, i32, cp, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    sig("ta_hamming_search_batch", i32, [sp, sp, sz, u32, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     _lib = L
     return L
 

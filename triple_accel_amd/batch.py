@@ -441,15 +441,41 @@ def levenshtein_search_batch(needles: Strings, haystacks: Strings, k, search_typ
     return matches, counts
 
 
+def hamming_search_batch(needles: Strings, haystacks: Strings, k, search_type=SearchType.Best, cap=None, matches=None, counts=None):
+    """hamming_search_simd_with_opts(needle_i, haystack_i, k, search_type) for every pair, on the device: -> (matches, counts), shaped as
+    levenshtein_search_batch's.  counts[i] (int32) = the length of pair i's result, or -1 where the single call panics (a NUL byte in
+    the haystack): that pair has no matches, the others are unaffected.  matches[i, :min(counts[i], cap)] = its first `cap` matches as
+    int64 (start, end, k) rows, positions relative to haystack i, in increasing start.  cap = 0: counts only.  needles may be
+    Strings.shared(needle, n): one needle for every pair.  Default cap: 8 (search_type Best) or 64 (All)."""
+    st = search_type
+    n, dev = haystacks.n, haystacks.blob.device
+    assert needles.n == n
+    if cap is None:
+        cap = 8 if st == SearchType.Best else 64
+    matches = torch.empty((n, cap, 3), dtype=torch.int64, device=dev) if matches is None else matches
+    counts = torch.empty(n, dtype=torch.int32, device=dev) if counts is None else counts
+    assert matches.dtype == torch.int64 and matches.is_contiguous() and matches.numel() >= n * cap * 3
+    assert counts.dtype == torch.int32 and counts.numel() >= n
+    rc = _n.lib().ta_hamming_search_batch(needles._ref(), haystacks._ref(), n, int(k), int(st),
+                                          matches.data_ptr() if cap else None, counts.data_ptr(), cap, _stream())
+    if rc:
+        _raise(rc)
+    return matches, counts
+
+
 def matches_to_lists(matches, counts, allow_cut=False):
-    """the device result of levenshtein_search_batch as Python lists of triple_accel_amd.Match per pair (host copy).  A result longer
-    than the `cap` rows of its pair was cut on the device (counts says how long it is): that is an error here, not a silently shorter
-    list, unless the caller asks for the cut lists (allow_cut)."""
-    from . import Match
+    """the device result of levenshtein_search_batch / hamming_search_batch as Python lists of triple_accel_amd.Match per pair (host
+    copy).  A result longer than the `cap` rows of its pair was cut on the device (counts says how long it is): that is an error here,
+    not a silently shorter list, unless the caller asks for the cut lists (allow_cut).  A negative count is hamming_search_batch's NUL
+    verdict: the reference's panic, raised here for the first such pair."""
+    from . import Match, PanicError
     m, c = matches.cpu().numpy(), counts.cpu().numpy().astype("int64")
     cap = m.shape[1]
+    nul = [i for i in range(len(c)) if int(c[i]) < 0]
+    if nul:
+        raise PanicError("No zero/null bytes allowed in the string! (pair %d)" % nul[0])
     cut = [i for i in range(len(c)) if int(c[i]) > cap]
     if cut and not allow_cut:
-        raise ValueError("levenshtein_search_batch: %d result(s) longer than cap = %d matches (first: pair %d with %d); pass a larger cap"
+        raise ValueError("search batch: %d result(s) longer than cap = %d matches (first: pair %d with %d); pass a larger cap"
                          % (len(cut), cap, cut[0], int(c[cut[0]])))
     return [[Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF) for r in m[i, :min(int(c[i]), cap)]] for i in range(len(c))]

@@ -1,0 +1,112 @@
+// ham_search_batch.hip -- gfx950 kernels of ta_hamming_search_batch: one lane per (needle, haystack) pair.
+//
+// General route: the SWAR window compare of ham_search_batch_body.h, the needle in registers up to 64 bytes (NW = 2 / 4 / 8 / 16 dwords),
+// both sides from memory beyond.  Shared-needle route (1..32 bytes, 4 k <= n): bit-sliced mismatch counters, the needle's 256-entry Mis
+// table built once per workgroup in LDS.  Every lane folds its own result (HamBatchSink) and writes its own count; the NUL scan of the
+// SIMD contract rides on the haystack words the scan loads.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+#include "ham_search_batch_body.h"
+#include "ta_internal.h"
+
+namespace ta {
+
+__device__ __forceinline__ void hb_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
+    if (s.off) {
+        const uint64_t o0 = s.off[i], o1 = s.off[i + 1];
+        p = s.blob + o0;
+        len = o1 - o0;
+    } else {
+        p = s.blob + (uint64_t)i * s.stride;
+        len = s.len;
+    }
+}
+
+template <int NW>
+__global__ __launch_bounds__(256) void ham_search_batch_kernel(HamBatchParams P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= P.n) return;
+    const uint32_t pair = P.list ? P.list[idx] : idx;
+    const uint8_t *np, *hay;
+    uint64_t nl, h;
+    hb_str(P.nd, pair, np, nl);
+    hb_str(P.hs, pair, hay, h);
+    P.counts[pair] = ham_batch_pair_regs<NW>(np, nl, hay, h, P.k, P.best != 0, P.matches + (uint64_t)pair * P.cap, P.cap);
+}
+
+__global__ __launch_bounds__(256) void ham_search_batch_mem_kernel(HamBatchParams P) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= P.n) return;
+    const uint32_t pair = P.list ? P.list[idx] : idx;
+    const uint8_t *np, *hay;
+    uint64_t nl, h;
+    hb_str(P.nd, pair, np, nl);
+    hb_str(P.hs, pair, hay, h);
+    P.counts[pair] = ham_batch_pair_mem(np, nl, hay, h, P.k, P.best != 0, P.matches + (uint64_t)pair * P.cap, P.cap);
+}
+
+// Shared needle: Mis[c] kept 64 times (hamming_search_bits_kernel's layout: lane l reads dword l of row c, so no two lanes of a 32-lane
+// group share a bank whatever the bytes are) -- 64 KB, 512 threads, two workgroups per CU.  The lookup's address is one v_perm of the
+// haystack dword: byte b << 8 | lane * 4.
+template <int B>
+__global__ __launch_bounds__(512) void ham_search_batch_bits_kernel(HamBatchParams P) {
+    __shared__ __attribute__((aligned(16))) uint32_t mis[256 * 64];
+    const uint8_t *needle = P.nd.blob;
+    const uint32_t nlen = P.max_needle;
+    {
+        const uint32_t m = ham_bits_mis(needle, nlen, threadIdx.x >> 1);
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 *row = (u32x4 *)(mis + (threadIdx.x >> 1) * 64 + (threadIdx.x & 1u) * 32);
+#pragma unroll
+        for (int q = 0; q < 8; q++) row[q] = u32x4{m, m, m, m};
+    }
+    __syncthreads();
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= P.n) return;
+    const uint32_t pair = P.list ? P.list[idx] : idx;
+    const uint32_t lane_off = (threadIdx.x & 63u) * 4u;
+    auto lookup = [&](uint32_t v, int b) -> uint32_t {
+        const uint32_t a = __builtin_amdgcn_perm(v, lane_off, 0x0C0C0000u | ((4u + (uint32_t)b) << 8));
+        return *(const uint32_t *)((const uint8_t *)mis + a);
+    };
+    const uint8_t *hay;
+    uint64_t h;
+    hb_str(P.hs, pair, hay, h);
+    P.counts[pair] = ham_batch_pair_bits<B>(needle, nlen, hay, h, P.k, P.best != 0, lookup, P.matches + (uint64_t)pair * P.cap, P.cap);
+}
+
+hipError_t ham_search_batch_launch(const HamBatchParams &P, bool bits, hipStream_t st) {
+    if (P.n == 0) return hipSuccess;
+    if (bits) {
+        const int planes = ham_bits_planes(P.k);
+        const dim3 grid((P.n + 511) / 512), block(512);
+        set_last_kernel_name("ham_search_batch_bits_kernel<%d>", planes);
+        switch (planes) {
+            case 1: hipLaunchKernelGGL(ham_search_batch_bits_kernel<1>, grid, block, 0, st, P); break;
+            case 2: hipLaunchKernelGGL(ham_search_batch_bits_kernel<2>, grid, block, 0, st, P); break;
+            case 3: hipLaunchKernelGGL(ham_search_batch_bits_kernel<3>, grid, block, 0, st, P); break;
+            case 4: hipLaunchKernelGGL(ham_search_batch_bits_kernel<4>, grid, block, 0, st, P); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    const dim3 grid((P.n + 255) / 256), block(256);
+    const uint32_t m = P.max_needle;
+    if (m > 64) {
+        set_last_kernel_name("ham_search_batch_mem_kernel");
+        hipLaunchKernelGGL(ham_search_batch_mem_kernel, grid, block, 0, st, P);
+        return hipGetLastError();
+    }
+    const int nw = m <= 8 ? 2 : m <= 16 ? 4 : m <= 32 ? 8 : 16;
+    set_last_kernel_name("ham_search_batch_kernel<%d>", nw);
+    switch (nw) {
+        case 2: hipLaunchKernelGGL(ham_search_batch_kernel<2>, grid, block, 0, st, P); break;
+        case 4: hipLaunchKernelGGL(ham_search_batch_kernel<4>, grid, block, 0, st, P); break;
+        case 8: hipLaunchKernelGGL(ham_search_batch_kernel<8>, grid, block, 0, st, P); break;
+        default: hipLaunchKernelGGL(ham_search_batch_kernel<16>, grid, block, 0, st, P); break;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace ta

@@ -219,6 +219,20 @@ hipError_t search_batch_maxlen_launch(const StrView &nd, const StrView &hs, uint
 hipError_t search_batch_exact_launch(const SearchBatchParams &P, bool trans, bool packed, uint32_t mem_lanes, hipStream_t st);
 hipError_t search_batch_scan_launch(const SearchBatchParams &P, bool trans, hipStream_t st);
 
+// ta_hamming_search_batch (ham_search_batch.hip): one lane per (needle, haystack) pair
+struct HamBatchParams {
+    StrView nd, hs;               // needles (the strided form with stride 0: one shared needle), haystacks
+    ta_match *matches;            // device: cap slots per pair
+    uint32_t *counts;             // device: the length of each pair's result, TA_NONE for a haystack with a NUL byte
+    uint64_t cap;
+    uint32_t n;                   // pairs
+    const uint32_t *list;         // the pairs in the order they are taken, or nullptr: 0..n
+    uint32_t k, best;
+    uint32_t max_needle;          // bound on every needle's length (the bit-sliced form: the shared needle's length)
+};
+// bits: the bit-sliced form (a shared needle of 1..32 bytes, 4 k <= its length); else the register form up to 64 bytes, the memory form beyond
+hipError_t ham_search_batch_launch(const HamBatchParams &P, bool bits, hipStream_t st);
+
 // ta_multi.hip: the device set (one worker thread per entry).  multi_search_shards / multi_pair_shards: over how many of them a host
 // haystack / a host batch of that size is spread (1: the calling thread's own device path).  The search forms return the All-mode hits
 // sorted by end (best: only those with each shard's smallest k -- all the Best fold can keep), without the end == 0 match.

@@ -1,6 +1,7 @@
-// ta_search_batch.hip -- ta_levenshtein_search_batch (include/triple_accel_amd.h): validation, route choice,
-// thread scratch and the launches of lev_search_batch.hip.  Everything is enqueued on the caller's stream; with every length
-// bound given (strided sides, or CSR max_len) there is no synchronisation and the call can be captured into a graph.
+// ta_search_batch.hip -- ta_levenshtein_search_batch and ta_hamming_search_batch (include/triple_accel_amd.h):
+// validation, route choice, thread scratch and the launches of lev_search_batch.hip / ham_search_batch.hip.  Everything is enqueued on
+// the caller's stream; with every length bound given (strided sides, or CSR max_len) there is no synchronisation and the call can be
+// captured into a graph.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -150,6 +151,51 @@ int ta_levenshtein_search_batch(const ta_strings *needles, const ta_strings *hay
         P.list = order;
     }
     TA_HIP(search_batch_exact_launch(P, trans, packed, mem_lanes, st));
+    return TA_OK;
+}
+
+int ta_hamming_search_batch(const ta_strings *needles, const ta_strings *haystacks, size_t n,
+                            uint32_t k, int search_type, ta_match *matches_dev, uint32_t *counts_dev, size_t cap, void *stream) {
+    if (!needles || !haystacks || (search_type != TA_SEARCH_ALL && search_type != TA_SEARCH_BEST) || n > 0xFFFFFFF0ull) {
+        set_last_error_msg("bad search batch arguments");
+        return TA_ERR_ARG;
+    }
+    if (n && (!needles->blob || !haystacks->blob || !counts_dev || (cap && !matches_dev))) { set_last_error_msg("null buffer"); return TA_ERR_ARG; }
+    if (cap && n > SIZE_MAX / sizeof(ta_match) / cap) { set_last_error_msg("n * cap overflows"); return TA_ERR_ARG; }
+    if ((!needles->off || needles->max_len) && (needles->off ? needles->max_len : needles->len) > 0xFFFFu) {
+        set_last_error_msg("needle longer than 65535 bytes");
+        return TA_ERR_ARG;
+    }
+    if ((!haystacks->off || haystacks->max_len) && (haystacks->off ? haystacks->max_len : haystacks->len) >> 32) {
+        set_last_error_msg("haystack of 2^32 bytes or more");
+        return TA_ERR_UNSUPPORTED;
+    }
+    if (!device_ready()) return TA_ERR_HIP;
+    if (n == 0) return TA_OK;
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard guard(st);
+    uint64_t max_n = 0, max_h = 0;
+    int rc = sb_max_lens(needles, haystacks, (uint32_t)n, st, &max_n, &max_h);
+    if (rc) return rc;
+    if (max_n > 0xFFFFu) { set_last_error_msg("needle longer than 65535 bytes"); return TA_ERR_ARG; }
+    if (max_h >> 32) { set_last_error_msg("haystack of 2^32 bytes or more"); return TA_ERR_UNSUPPORTED; }
+
+    HamBatchParams P = {};
+    P.nd = sb_view(needles); P.hs = sb_view(haystacks);
+    P.matches = matches_dev; P.counts = counts_dev; P.cap = cap; P.n = (uint32_t)n;
+    P.k = k; P.best = search_type == TA_SEARCH_BEST ? 1u : 0u;
+    P.max_needle = (uint32_t)max_n;
+    // the bit-sliced form: one needle for every pair, 1..32 bytes, k at most a quarter of its length (so k <= 8: at most four counter
+    // planes).  A window that passes the counters is recounted from memory, so the form is kept to thresholds where such windows are
+    // rare whatever the alphabet; beyond, the general route counts every window exactly in registers
+    const bool shared = !needles->off && needles->stride == 0;
+    const bool bits = shared && max_n >= 1 && max_n <= 32 && 4ull * k <= max_n && !env_int("TA_HSEARCH_BATCH_GENERAL");
+    if (haystacks->off && n >= 4096 && max_h >= 16) {
+        const uint32_t *order = nullptr;
+        if ((rc = sb_order(haystacks, (uint32_t)n, max_h, st, &order))) return rc;
+        P.list = order;
+    }
+    TA_HIP(ham_search_batch_launch(P, bits, st));
     return TA_OK;
 }
 
