@@ -36,8 +36,13 @@ __global__ __launch_bounds__(64 * BITS_WAVES_PER_BLOCK) void lev_bits_line_kerne
 }
 
 // stride-8 form (bands of up to 33 diagonals), either fetch form
+#ifdef TA_S8_WAVES_PER_SIMD           // A/B builds only: cap the registers for this many wavefronts per SIMD
+#define TA_S8_ATTR __attribute__((amdgpu_waves_per_eu(TA_S8_WAVES_PER_SIMD, TA_S8_WAVES_PER_SIMD)))
+#else
+#define TA_S8_ATTR
+#endif
 template <bool TRANS, bool LINE, bool EARLY = false>
-__global__ __launch_bounds__(64 * BITS_WAVES_PER_BLOCK) void lev_bits_s8_kernel(LevParams P) {
+__global__ __launch_bounds__(64 * BITS_WAVES_PER_BLOCK) TA_S8_ATTR void lev_bits_s8_kernel(LevParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     LevParams Q = P;
     if (P.n_dev) Q.n = *P.n_dev;                       // the pairs of a list a kernel before this one wrote (lev_bitsq's fallback)

@@ -25,6 +25,7 @@
 #pragma once
 #include <type_traits>
 
+#include "bitop3.h"
 #include "lev_band_body.h"
 
 namespace ta {
@@ -160,6 +161,15 @@ struct LevBits {
         if (TRANS && ONEBIT) st.PMp[NW - 1] = pm_bot;
     }
 
+    // a node of step8's gather tree: (a & m) | (b & ~m)
+    static TA_HD inline __attribute__((always_inline)) U32 tree_bfi(uint32_t m, const U32 &a, const U32 &b) {
+#ifdef TA_S8_TREE_BITOP3
+        return bitop3<0xCA>(W::splat(m), a, b);
+#else
+        return W::bfi_k(m, a, b);
+#endif
+    }
+
     // S8: iteration tp with C = tp % 8, warm-up or column.  Before it, register r holds the bytes of window bits
     // ((r - C) & 7) + 8 q; b_dw / a_raw = the dwords whose byte C & 3 is this iteration's column character / the byte of `a` that
     // enters (it is the bottom diagonal's byte now and the top byte of register C afterwards); a_x = a_raw ^ 0x0C0C0C0C.
@@ -173,34 +183,43 @@ struct LevBits {
             U32 M[8];
 #pragma unroll
             for (int m = 0; m < 8; m++) M[m] = W::ne12(st.AW[(C + m) & 7] ^ Bs);
-            const U32 q01 = W::bfi_k(0x01010101u, M[0], M[1]), q23 = W::bfi_k(0x04040404u, M[2], M[3]);
-            const U32 q45 = W::bfi_k(0x10101010u, M[4], M[5]), q67 = W::bfi_k(0x40404040u, M[6], M[7]);
-            const U32 t = W::bfi_k(0x0F0F0F0Fu, W::bfi_k(0x03030303u, q01, q23), W::bfi_k(0x30303030u, q45, q67));
-            const U32 PM = ~t;
-            U32 sum, D0, d0_bot;
+            const U32 q01 = tree_bfi(0x01010101u, M[0], M[1]), q23 = tree_bfi(0x04040404u, M[2], M[3]);
+            const U32 q45 = tree_bfi(0x10101010u, M[4], M[5]), q67 = tree_bfi(0x40404040u, M[6], M[7]);
+            // PM = ~t, t the mismatch mask: the tree's last node with the inversion folded in (table 0x35 = ~bfi).  The recurrence in 12 operations,
+            // every three-input one through bitop3<> so that it reaches the instruction selector as written (left to itself hipcc chains lazily
+            // inverted v_bitop3 through PM, D0, HP, HN, VP', VN': 14 instructions).  With X = ((PM & VP) + VP) ^ VP | PM, D0 = X | VN and VP, VN disjoint:
+            //     HN = D0 & VP = X & VP            HP = VN | ~(D0 | VP) = VN | ~(X | VP)      (VN | ~(VN | y) = VN | ~y)
+            // so HP and HN do not wait for D0, which then feeds only the two v_alignbit (and REC / CKPT).  TRANS: the transposition term ORs into
+            // D0 behind X | VN; HP and HN are taken from that final D0 (the term's bits are not in X).
+            const U32 PM = bitop3<0x35>(W::splat(0x0F0F0F0Fu), tree_bfi(0x03030303u, q01, q23), tree_bfi(0x30303030u, q45, q67));
+            const U32 pv = PM & st.VP[0];
+            U32 sum, D0, d0_bot, HP, HN;
             if constexpr (TRANS) {
                 const Bool m_bot = W::template byte_eq<(C & 3)>(a_raw, b_dw);
                 Bool carry = W::bfalse();
-                W::addc(PM & st.VP[0], st.VP[0], carry, sum, carry);
-                D0 = ((sum ^ st.VP[0]) | PM) | st.VN[0];
+                W::addc(pv, st.VP[0], carry, sum, carry);
+                const U32 X = bitop3<0xBE>(sum, st.VP[0], PM);          // (sum ^ VP) | PM
                 // as column(): the bottom diagonal's own match bit of the column before is st.PMp[NW - 1] bit 0
                 const U32 pml = PM << 1, pmr = W::template alignbit<1>(st.PMp[NW - 1], st.PMp[0]);
-                D0 = D0 | (~st.D0p[0] & pml & pmr);
+                D0 = bitop3<0xFE>(X, st.VN[0], bitop3<0x08>(st.D0p[0], pml, pmr));      // X | VN | (~D0_prev & pml & pmr)
                 d0_bot = W::sel(carry | m_bot, W::splat(1), W::splat(0));          // ONEBIT: match | carry, in bit 0
                 st.PMp[NW - 1] = W::sel(m_bot, W::splat(1), W::splat(0));
+                HP = bitop3<0xF1>(st.VN[0], D0, st.VP[0]);              // VN | ~(D0 | VP)
+                HN = D0 & st.VP[0];
             } else {
                 // the carry stays a wavefront mask (SGPR pair) from the addition to the bottom diagonal's match | carry: the byte
                 // compare is one SDWA v_cmp, two VALU instructions for the 33rd diagonal instead of three
-                const typename W::Mask cm = W::add_carry_mask(PM & st.VP[0], st.VP[0], sum);
-                D0 = ((sum ^ st.VP[0]) | PM) | st.VN[0];
+                const typename W::Mask cm = W::add_carry_mask(pv, st.VP[0], sum);
+                const U32 X = bitop3<0xBE>(sum, st.VP[0], PM);          // (sum ^ VP) | PM
+                D0 = X | st.VN[0];
                 d0_bot = W::template byte_eq_or<(C & 3)>(a_raw, b_dw, cm);
+                HP = bitop3<0xF1>(st.VN[0], X, st.VP[0]);               // VN | ~(X | VP)
+                HN = X & st.VP[0];
             }
             st.acc = W::template alignbit<1>(CAP ? W::sel(live, D0, W::splat(0)) : D0, st.acc);
-            const U32 HP = st.VN[0] | ~(D0 | st.VP[0]);
             if (REC) { st.rD0 = D0; st.rBot = d0_bot; st.rHP = HP; }
-            const U32 HN = D0 & st.VP[0];
             const U32 D0s = W::template alignbit<1>(d0_bot, D0);
-            st.VP[0] = HN | ~(D0s | HP);
+            st.VP[0] = bitop3<0xF1>(HN, D0s, HP);                       // HN | ~(D0s | HP)
             st.VN[0] = D0s & HP;
             if (TRANS) { st.PMp[0] = PM; st.D0p[0] = D0; }
         }
