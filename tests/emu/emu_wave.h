@@ -5,9 +5,17 @@
 // never a fallback: the product's compute entry points fail with TA_ERR_HIP without a GPU.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "wave.h"
+
+// a precondition of the vocabulary (wave.h): a body that breaks one aborts in the CPU suite instead of silently agreeing with itself
+#define TA_EMU_REQUIRE(cond, what)                                                                  \
+    do {                                                                                            \
+        if (!(cond)) { fprintf(stderr, "EmuWave: precondition broken -- %s\n", what); abort(); }    \
+    } while (0)
 
 namespace ta {
 
@@ -78,9 +86,9 @@ struct EmuWave {
     static U32 sdot4(const U32 &a, const U32 &b, const U32 &acc) {
         V32 r;
         for (int i = 0; i < 64; i++) {
-            int32_t t = (int32_t)acc.v[i];
-            for (int k = 0; k < 4; k++) t += (int32_t)(int8_t)(a.v[i] >> (8 * k)) * (int32_t)(int8_t)(b.v[i] >> (8 * k));
-            r.v[i] = (uint32_t)t;
+            uint32_t t = acc.v[i];          // no clamp: the sum wraps modulo 2^32 (unsigned arithmetic -- signed overflow is undefined)
+            for (int k = 0; k < 4; k++) t += (uint32_t)((int32_t)(int8_t)(a.v[i] >> (8 * k)) * (int32_t)(int8_t)(b.v[i] >> (8 * k)));
+            r.v[i] = t;
         }
         return r;
     }
@@ -105,7 +113,9 @@ struct EmuWave {
     template <int N> static U32 alignbit(const U32 &hi, const U32 &lo) {
         V32 r; for (int i = 0; i < 64; i++) r.v[i] = (uint32_t)(((((uint64_t)hi.v[i]) << 32) | lo.v[i]) >> N); return r;
     }
-    static U32 bfe(const U32 &x, uint32_t off, uint32_t width) { V32 r; for (int i = 0; i < 64; i++) r.v[i] = (x.v[i] >> off) & ((1u << width) - 1u); return r; }
+    static U32 bfe(const U32 &x, uint32_t off, uint32_t width) {
+        TA_EMU_REQUIRE(width >= 1u && width < 32u && off + width <= 32u, "bfe: 1 <= width < 32, off + width <= 32");
+        V32 r; for (int i = 0; i < 64; i++) r.v[i] = (x.v[i] >> off) & ((1u << width) - 1u); return r; }
     static U32 lshl_add(const U32 &a, uint32_t s, const U32 &b) { V32 r; for (int i = 0; i < 64; i++) r.v[i] = (a.v[i] << s) + b.v[i]; return r; }
     static U32 alignbyte_v(const U32 &hi, const U32 &lo, const U32 &s) {
         V32 r; for (int i = 0; i < 64; i++) r.v[i] = (uint32_t)(((((uint64_t)hi.v[i]) << 32) | lo.v[i]) >> (8 * (s.v[i] & 3u))); return r; }
@@ -212,26 +222,31 @@ struct EmuWave {
     static U32 splat_byte_n(const U32 &x) { V32 r; for (int i = 0; i < 64; i++) r.v[i] = ((x.v[i] >> (8 * N)) & 0xffu) * 0x01010101u; return r; }
     template <int N>
     static U32 slide_in_byte(const U32 &hi, const U32 &lo) { V32 r; for (int i = 0; i < 64; i++) r.v[i] = (lo.v[i] >> 8) | (((hi.v[i] >> (8 * N)) & 0xffu) << 24); return r; }
+    // one output byte of v_perm_b32 over the eight source bytes {hi: 4..7, lo: 0..3}, the whole selector table: 0..7 a source byte,
+    // 8..11 the sign bit of byte 1 / 3 / 5 / 7 in all eight bits, 12 the constant 0x00, 13..255 the constant 0xFF
+    static uint32_t perm_byte(uint64_t src, uint32_t s) {
+        if (s >= 13u) return 0xffu;
+        if (s == 12u) return 0x00u;
+        if (s >= 8u) return ((src >> (16u * (s - 8u) + 15u)) & 1u) ? 0xffu : 0x00u;
+        return (uint32_t)((src >> (8u * s)) & 0xffu);
+    }
     template <uint32_t SEL>
-    static U32 perm(const U32 &hi, const U32 &lo) {            // selectors 0..7 (and 0x0C = the constant 0x00): all the bodies use
+    static U32 perm(const U32 &hi, const U32 &lo) {
         V32 r;
         for (int i = 0; i < 64; i++) {
             const uint64_t src = ((uint64_t)hi.v[i] << 32) | lo.v[i];
             uint32_t o = 0;
-            for (int k = 0; k < 4; k++) {
-                const uint32_t s = (SEL >> (8 * k)) & 0xffu;
-                o |= (s < 8u ? (uint32_t)((src >> (8 * s)) & 0xffu) : 0u) << (8 * k);
-            }
+            for (int k = 0; k < 4; k++) o |= perm_byte(src, (SEL >> (8 * k)) & 0xffu) << (8 * k);
             r.v[i] = o;
         }
         return r;
     }
-    static U32 perm_sel(const U32 &hi, const U32 &lo, const U32 &sel) {        // selectors 0..7 only
+    static U32 perm_sel(const U32 &hi, const U32 &lo, const U32 &sel) {
         V32 r;
         for (int i = 0; i < 64; i++) {
             const uint64_t src = ((uint64_t)hi.v[i] << 32) | lo.v[i];
             uint32_t o = 0;
-            for (int k = 0; k < 4; k++) o |= (uint32_t)((src >> (8 * ((sel.v[i] >> (8 * k)) & 7u))) & 0xffu) << (8 * k);
+            for (int k = 0; k < 4; k++) o |= perm_byte(src, (sel.v[i] >> (8 * k)) & 0xffu) << (8 * k);
             r.v[i] = o;
         }
         return r;
@@ -269,8 +284,8 @@ struct EmuWave {
         for (int i = 0; i < 64; i++) if (pred.v[i]) { uint32_t t; memcpy(&t, lds + off.v[i], 4); t |= v.v[i]; memcpy(lds + off.v[i], &t, 4); }
     }
     static void mem_fence() {}
-    static uint32_t readlane(const U32 &x, uint32_t l) { return x.v[l & 63]; }
-    static U32 writelane(const U32 &x, uint32_t v, uint32_t l) { V32 r = x; r.v[l & 63] = v; return r; }
+    static uint32_t readlane(const U32 &x, uint32_t l) { TA_EMU_REQUIRE(l < 64u, "readlane: l < 64"); return x.v[l]; }
+    static U32 writelane(const U32 &x, uint32_t v, uint32_t l) { TA_EMU_REQUIRE(l < 64u, "writelane: l < 64"); V32 r = x; r.v[l] = v; return r; }
     static U32 gload_u8(const Ptr &p, const Bool &pred) { V32 r; for (int i = 0; i < 64; i++) r.v[i] = pred.v[i] ? *p.v[i] : 0u; return r; }
     static uint32_t wave_sum(const U32 &x) { uint32_t t = 0; for (int i = 0; i < 64; i++) t += x.v[i]; return t; }
     static void lds_wave_sync() {}

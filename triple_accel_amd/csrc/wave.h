@@ -84,7 +84,8 @@ struct DevWave {
     static __device__ __forceinline__ U32 bcnt(U32 x, U32 acc) { return (U32)__builtin_popcount(x) + acc; }
     // ({hi,lo} >> N)[31:0], N in 1..31 -> v_alignbit_b32
     template <int N> static __device__ __forceinline__ U32 alignbit(U32 hi, U32 lo) { return __builtin_amdgcn_alignbit(hi, lo, N); }
-    // bits [off, off + width) of x -> v_bfe_u32 (kept opaque so that a following shift is not folded back into a mask)
+    // bits [off, off + width) of x -> v_bfe_u32 (kept opaque so that a following shift is not folded back into a mask).
+    // Contract: 1 <= width < 32 and off + width <= 32 (no body asks for more; EmuWave aborts outside it)
     static __device__ __forceinline__ U32 bfe(U32 x, uint32_t off, uint32_t width) { return __builtin_amdgcn_ubfe(x, off, width); }
     // NOTE: no real instructions in inline asm in this file -- hipcc's hazard recogniser does not look inside asm
     // statements (a v_dot4 result consumed by an asm VALU instruction two slots later read a stale value on gfx950).
@@ -109,7 +110,8 @@ struct DevWave {
     static __device__ __forceinline__ U32 from_upper(U32 x, U32 fill) {
         return (U32)__builtin_amdgcn_update_dpp((int)fill, (int)x, 0x130, 0xf, 0xf, false);
     }
-    // same moves when the edge lane's value is overridden by the caller anyway: no tied `old` operand
+    // same moves when the edge lane's value is overridden by the caller anyway: no tied `old` operand (the edge lane reads 0 here,
+    // 0xDEADBEEF in EmuWave: a body must not use it)
     static __device__ __forceinline__ U32 from_lower0(U32 x) { return (U32)__builtin_amdgcn_mov_dpp((int)x, 0x138, 0xf, 0xf, true); }
     static __device__ __forceinline__ U32 from_upper0(U32 x) { return (U32)__builtin_amdgcn_mov_dpp((int)x, 0x130, 0xf, 0xf, true); }
     static __device__ __forceinline__ U32 shfl(U32 x, U32 src_lane) {
@@ -348,10 +350,11 @@ struct DevWave {
     // (lo >> 8) | (byte N of hi << 24): the dword slides one byte down, byte N of `hi` enters on top -> one v_perm_b32
     template <int N>
     static __device__ __forceinline__ U32 slide_in_byte(U32 hi, U32 lo) { return __builtin_amdgcn_perm(hi, lo, 0x00030201u | ((4u + (uint32_t)N) << 24)); }
-    // bytes picked by the constant selector SEL out of {hi: 4..7, lo: 0..3} (0x0C: the constant 0x00) -> v_perm_b32
+    // bytes picked by the constant selector SEL out of {hi: 4..7, lo: 0..3} -> v_perm_b32.  The whole selector table holds on both
+    // policies: 8..11 the sign bit of byte 1 / 3 / 5 / 7 in all eight bits, 0x0C the constant 0x00, 0x0D..0xFF the constant 0xFF
     template <uint32_t SEL>
     static __device__ __forceinline__ U32 perm(U32 hi, U32 lo) { return __builtin_amdgcn_perm(hi, lo, SEL); }
-    // the same with a per-lane selector (bytes 0..3: lo, 4..7: hi) -> v_perm_b32
+    // the same with a per-lane selector (bytes 0..3: lo, 4..7: hi, the other codes as above) -> v_perm_b32
     static __device__ __forceinline__ U32 perm_sel(U32 hi, U32 lo, U32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
     // x >> s and ({hi,lo} >> s)[31:0] with a wave-uniform run-time s (< 32): v_lshrrev_b32 / v_alignbit_b32 with a scalar shift
     static __device__ __forceinline__ U32 shr_u(U32 x, uint32_t s) { return x >> s; }
@@ -417,9 +420,10 @@ struct DevWave {
     }
     // this wave's global stores become visible to its own later global loads from other lanes (L1 invalidate)
     static __device__ __forceinline__ void mem_fence() { __threadfence(); }
-    // value of x in lane l (l wave-uniform) -> v_readlane_b32
+    // value of x in lane l (l wave-uniform, l < 64) -> v_readlane_b32
     static __device__ __forceinline__ uint32_t readlane(U32 x, uint32_t l) { return __builtin_amdgcn_readlane(x, l); }
-    // x with lane l (wave-uniform) replaced by the wave-uniform value v (v_cmp + v_cndmask; hipcc has no writelane builtin)
+    // x with lane l (wave-uniform, l < 64: a larger l names no lane here, EmuWave aborts) replaced by the wave-uniform value v
+    // (v_cmp + v_cndmask; hipcc has no writelane builtin)
     static __device__ __forceinline__ U32 writelane(U32 x, uint32_t v, uint32_t l) { return lane() == l ? v : x; }
     static __device__ __forceinline__ U32 gload_u8(Ptr p, Bool pred) { return pred ? (U32)*p : 0u; }
     static __device__ __forceinline__ uint32_t wave_sum(U32 x) {
