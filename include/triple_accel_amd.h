@@ -323,6 +323,38 @@ int ta_hamming_search_batch(const ta_strings *needles, const ta_strings *haystac
                             uint32_t k, int search_type,
                             ta_match *matches_dev, uint32_t *counts_dev, size_t cap, void *stream);
 
+/* Every query against every target within k, on device-resident data (no reference analogue: the reference takes one pair per call).
+ * The pair (q, t) is a hit with distance d exactly when ta_levenshtein_simd_k_with_opts(query q, target t, k, 0, costs) gives d and not
+ * TA_NONE (levenshtein_simd_k_with_opts, src/levenshtein.rs:714-720).  *count_dev = the number of hits whatever `cap` is;
+ * hits_dev[0 .. min(count, cap)) holds that many DISTINCT hits {query, target, k = d, pad_ = 0} in no particular order (an atomic cursor);
+ * when count > cap, which hits are kept is unspecified -- each kept one is a true hit and none appears twice.  cap = 0 asks for the count
+ * only, hits_dev may then be NULL.  nearest_dev, when not NULL, gets for every query q the word (uint64_t)d << 32 | t that is smallest
+ * over the hits of q -- the smallest distance, at equal distance the lowest target index -- and all ones when q has no hit; it does not
+ * depend on cap.  Nothing of size nq x nt is allocated or written: the caller no longer gathers the pairs for ta_levenshtein_k_batch.
+ * Both sides take the strided and the CSR form and follow the TA_BLOB_SLACK rule.
+ * Costs: LEVENSHTEIN_COSTS, RDAMERAU_COSTS and their multiples EditCosts(g, g, 0, None | Some(g)) (run with k / g, reported as g d, as the
+ * batch entries do); any other valid EditCosts: TA_ERR_UNSUPPORTED; invalid ones: TA_ERR_BAD_COSTS.  Every QUERY is at most 64 bytes: a
+ * longer bound (the strided len, the CSR max_len given or measured) is TA_ERR_UNSUPPORTED; targets may have any length below 2^32
+ * (TA_ERR_UNSUPPORTED beyond).  The distance is symmetric under these costs: a caller whose short side is the other one swaps the
+ * arguments (and the two index fields of the records).
+ * TA_ERR_ARG: NULL queries / targets / costs / count_dev; with nq, nt > 0 a NULL blob; cap > 0 with NULL hits_dev; nq or nt of 2^32 or
+ * more; cap * sizeof(ta_cross_hit) overflowing.  All of these come before any device work.  No device: TA_ERR_HIP.  nq == 0 or nt == 0:
+ * TA_OK, the count zero (and every nearest word all ones).
+ * The call enqueues its work on `stream` and returns without synchronising; the counter and nearest_dev are initialised by kernels.  With
+ * every length bound known (strided sides, CSR max_len given on both) it is capturable under the rule above (run once outside the
+ * capture first); a CSR side with max_len = 0 costs one synchronisation to measure it.  ta_last_kernel_name names the kernel
+ * (DESIGN.md 3.13). */
+typedef struct {
+    uint32_t query;
+    uint32_t target;
+    uint32_t k;
+    uint32_t pad_;           /* 0 */
+} ta_cross_hit;
+int ta_levenshtein_cross(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt,
+                         uint32_t k, const ta_edit_costs *costs,
+                         ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                         uint64_t *nearest_dev /* nq entries, or NULL */, void *stream);
+
 /* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
  * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
  * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of

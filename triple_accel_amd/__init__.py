@@ -382,6 +382,37 @@ def hamming_search_many(needle_or_needles, haystacks, k=None, search_type=Search
     return B.matches_to_lists(m, c)
 
 
+def _cross_sides(queries, targets):
+    from . import batch as B
+    return B.Strings.from_list([_b(q) for q in queries]), B.Strings.from_list([_b(t) for t in targets])
+
+
+def levenshtein_cross_many(queries, targets, k, costs=LEVENSHTEIN_COSTS):
+    """Every query against every target in ONE device call (ta_levenshtein_cross): the sorted list of (q, t, d) with d =
+    levenshtein_simd_k_with_opts(queries[q], targets[t], k, false, costs) for every pair where that is not None.  Unit-cost families
+    and their multiples; queries of at most 64 bytes (swap the sides otherwise).  Both lists are uploaded; when there are more hits than
+    the first call's room, one more call runs with room for the count it reported."""
+    from . import batch as B
+    qs, ts = _cross_sides(queries, targets)
+    k = _k(k)
+    hits, count, _ = B.levenshtein_cross(qs, ts, k, costs)
+    n = int(count.cpu()[0].item())
+    if n > hits.shape[0]:
+        hits, count, _ = B.levenshtein_cross(qs, ts, k, costs, cap=n)
+    q, t, d = B.cross_to_arrays(hits, count)
+    return [(int(a), int(b), int(c)) for a, b, c in zip(q, t, d)]
+
+
+def levenshtein_nearest_many(queries, targets, k, costs=LEVENSHTEIN_COSTS):
+    """For every query its nearest target within k, in ONE device call (ta_levenshtein_cross, counting only): a list of
+    (target, distance) -- the smallest distance, at equal distance the lowest target index -- or None where no target is within k."""
+    from . import batch as B
+    qs, ts = _cross_sides(queries, targets)
+    _, _, nearest = B.levenshtein_cross(qs, ts, _k(k), costs, cap=0, nearest=True)
+    words = nearest.cpu().numpy().view("uint64")
+    return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32) for w in words]
+
+
 def levenshtein_select(a_len, b_len, k, costs=LEVENSHTEIN_COSTS):
     """The dispatcher arithmetic (src/levenshtein.rs:731-791): (max_k, unit_k, cell_bits, ref_lanes)."""
     s = _n.LevSelectC()

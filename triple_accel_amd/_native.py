@@ -35,6 +35,8 @@ ABI_SYMBOLS = [
     "ta_levenshtein_k_batch_tokens", "ta_levenshtein_exp_batch_tokens", "ta_levenshtein_trace_batch_tokens", "ta_levenshtein_tokens",
     # search over a batch of (needle, haystack) pairs (ta_search_batch.hip)
     "ta_levenshtein_search_batch", "ta_hamming_search_batch",
+    # every query against every target (ta_cross.hip)
+    "ta_levenshtein_cross",
 ]
 
 
@@ -58,6 +60,10 @@ class LevSelectC(C.Structure):
 class LaunchInfoC(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("kernel", "diags_per_lane", "lanes_per_pair", "pairs_per_wave",
                                           "band_offset", "cell_bits", "affine", "transpose", "grid", "lds_bytes")]
+
+
+class CrossHitC(C.Structure):
+    _fields_ = [("query", C.c_uint32), ("target", C.c_uint32), ("k", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class StringsC(C.Structure):
@@ -184,6 +190,7 @@ def lib():
     sig("ta_levenshtein_tokens", i32, [C.c_void_p, sz, C.c_void_p, sz, u32, cp, u32p, epp, szp])
     sig("ta_levenshtein_search_batch", i32, [sp, sp, sz, u32, i32, cp, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     sig("ta_hamming_search_batch", i32, [sp, sp, sz, u32, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
+    sig("ta_levenshtein_cross", i32, [sp, sz, sp, sz, u32, cp, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p])
     _lib = L
     return L
 

@@ -479,3 +479,46 @@ def matches_to_lists(matches, counts, allow_cut=False):
         raise ValueError("search batch: %d result(s) longer than cap = %d matches (first: pair %d with %d); pass a larger cap"
                          % (len(cut), cap, cut[0], int(c[cut[0]])))
     return [[Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF) for r in m[i, :min(int(c[i]), cap)]] for i in range(len(c))]
+
+
+def levenshtein_cross(queries: Strings, targets: Strings, k, costs=LEVENSHTEIN_COSTS, cap=None, hits=None, count=None, nearest=False):
+    """Every query against every target within k, on the device (ta_levenshtein_cross): -> (hits, count, nearest).  The pair (q, t) is a
+    hit with distance d exactly when levenshtein_simd_k_with_opts(query q, target t, k, false, costs) is Some(d).  count (int64, one
+    element) = the number of hits whatever cap is; hits[:min(count, cap)] = that many distinct hits as int32 (query, target, d, 0) rows in
+    no particular order (cross_to_arrays sorts them).  cap = 0: the count only.  nearest = True (or an int64 tensor of queries.n elements
+    to reuse): nearest[q] = d << 32 | t of query q's nearest target -- the smallest distance, then the lowest index -- and -1 where q has
+    no hit, whatever cap is; else None.  LEVENSHTEIN_COSTS, RDAMERAU_COSTS and their multiples (g, g, 0, None | g); queries of at most 64
+    bytes (swap the sides when the short strings are the targets: the distance is symmetric).  Default cap: room for eight hits per
+    string of the longer side (at least 1,024, at most every pair).  Nothing is synchronised: read count before trusting hits."""
+    nq, nt, dev = queries.n, targets.n, targets.blob.device
+    if cap is None:
+        cap = hits.numel() // 4 if hits is not None else min(nq * nt, max(1024, 8 * max(nq, nt)))
+    hits = torch.empty((cap, 4), dtype=torch.int32, device=dev) if hits is None else hits
+    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+    if nearest is True:
+        nearest = torch.empty(nq, dtype=torch.int64, device=dev)
+    elif nearest is False:
+        nearest = None
+    assert hits.dtype == torch.int32 and hits.is_contiguous() and hits.numel() >= cap * 4
+    assert count.dtype == torch.int64 and count.numel() >= 1
+    assert nearest is None or (nearest.dtype == torch.int64 and nearest.is_contiguous() and nearest.numel() >= nq)
+    cc = _costs(costs)._c()
+    rc = _n.lib().ta_levenshtein_cross(queries._ref(), nq, targets._ref(), nt, int(k), _C.byref(cc), hits.data_ptr() if cap else None,
+                                       count.data_ptr(), cap, None if nearest is None else nearest.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return hits, count, nearest
+
+
+def cross_to_arrays(hits, count, allow_cut=False):
+    """the device result of levenshtein_cross as numpy arrays (query, target, k), sorted by (query, target) (host copy).  More hits than
+    the `cap` rows of `hits` were cut on the device (count says how many there are): that is an error here, not a silently shorter
+    result, unless the caller asks for the cut one (allow_cut)."""
+    import numpy as np
+    n, cap = int(count.cpu()[0].item()), hits.shape[0]
+    if n > cap and not allow_cut:
+        raise ValueError("cross: %d hits for cap = %d records; pass a larger cap" % (n, cap))
+    h = hits[:min(n, cap)].cpu().numpy().view(np.uint32).reshape(-1, 4)
+    order = np.lexsort((h[:, 1], h[:, 0]))
+    h = h[order]
+    return h[:, 0].copy(), h[:, 1].copy(), h[:, 2].copy()

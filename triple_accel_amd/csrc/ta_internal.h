@@ -34,7 +34,7 @@ struct Scratch {
     void release();
     ~Scratch();
 };
-constexpr int TA_SCRATCH_SLOTS = 30;   // 18..22: the token entries (ta_tokens.hip); 23..29: the search batch (ta_search_batch.hip)
+constexpr int TA_SCRATCH_SLOTS = 31;   // 18..22: the token entries (ta_tokens.hip); 23..29: the search batch (ta_search_batch.hip); 30: ta_cross.hip
 constexpr int TA_SLOT_SEARCH_HAY = 17;        // the host search entries' haystack staging: nothing else writes it (ta_levenshtein_search_resume relies on that)
 Scratch &tls_scratch(int which);
 
@@ -232,6 +232,20 @@ struct HamBatchParams {
 };
 // bits: the bit-sliced form (a shared needle of 1..32 bytes, 4 k <= its length); else the register form up to 64 bytes, the memory form beyond
 hipError_t ham_search_batch_launch(const HamBatchParams &P, bool bits, hipStream_t st);
+
+// ta_levenshtein_cross (lev_cross.hip): one lane per target, a wavefront walks a tile of queries
+struct CrossParams {
+    StrView q, t;                 // queries (every one at most 32 nw bytes), targets
+    uint32_t nq, nt;
+    uint32_t k, g;                // the unit threshold; distances are reported times g (lev_unit_scale, 1 for the unit families)
+    uint32_t qtile;               // queries per wavefront: ceil(nq / qtile) <= 65535
+    ta_cross_hit *hits;           // device: cap records, or nullptr with cap = 0
+    uint64_t cap;
+    unsigned long long *count;    // device, pre-zeroed
+    unsigned long long *nearest;  // device: nq words preset to all ones, or nullptr
+};
+constexpr uint32_t CROSS_MIN_QTILE = 16;
+hipError_t lev_cross_launch(const CrossParams &P, int nw, bool trans, hipStream_t st);
 
 // ta_multi.hip: the device set (one worker thread per entry).  multi_search_shards / multi_pair_shards: over how many of them a host
 // haystack / a host batch of that size is spread (1: the calling thread's own device path).  The search forms return the All-mode hits
