@@ -355,6 +355,36 @@ int ta_levenshtein_cross(const ta_strings *queries, size_t nq, const ta_strings 
                          ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
                          uint64_t *nearest_dev /* nq entries, or NULL */, void *stream);
 
+/* Every query against every target within k MISMATCHES, on device-resident data: the Hamming twin of ta_levenshtein_cross, for sets of
+ * fixed-length tags -- cell barcodes against a whitelist, a UMI set against itself, sample indices against a sheet -- where substitution
+ * is the only error considered (at k = 1 Levenshtein also accepts a shifted tag).  The pair (q, t) is a hit with distance d exactly when
+ * the two strings have the same length and ta_hamming(query q, target t) gives d <= k (hamming, src/hamming.rs:390).  Strings of
+ * different lengths are never a hit (the reference panics there, ta_hamming_batch answers TA_NONE); two empty strings are a hit with
+ * d = 0.  Bytes are opaque: 0x00 is an ordinary symbol (the NUL rule belongs to hamming_search only).
+ * *count_dev, hits_dev[0 .. min(count, cap)) and nearest_dev follow ta_levenshtein_cross's rules word for word: the count is exact
+ * whatever `cap` is, kept records are distinct {query, target, k = d, pad_ = 0} in no particular order, cap = 0 asks for the count only
+ * (hits_dev may then be NULL), nearest_dev[q] = the smallest (uint64_t)d << 32 | t over q's hits, all ones when there is none.
+ * per_query_dev, when not NULL, gets the number of hits of every query, whatever `cap` is: with nearest_dev it answers the
+ * demultiplexer's question "exactly one whitelist entry within k?".  flags = TA_CROSS_UPPER restricts EVERY output (count, hits, nearest,
+ * per-query) to the pairs with target index > query index: a set against itself gives each unordered pair once and no (i, i); a
+ * wavefront whose 64 targets all lie at or below a query does not compare that query.  Any other flag bit: TA_ERR_ARG.
+ * Every QUERY is at most 64 bytes: a longer bound (the strided len, the CSR max_len given or measured) is TA_ERR_UNSUPPORTED; targets
+ * may have any length below 2^32 (TA_ERR_UNSUPPORTED beyond), those longer than 64 bytes are never hits and are not read.  Both sides take
+ * the strided and the CSR form at any byte alignment and follow the TA_BLOB_SLACK rule.  Nothing of size nq x nt is allocated or written.
+ * TA_ERR_ARG: NULL queries / targets / count_dev; an unknown flag bit; nq or nt of 2^32 or more; with nq, nt > 0 a NULL blob; cap > 0 with
+ * NULL hits_dev; cap * sizeof(ta_cross_hit) overflowing.  All of these come before any device work.  No device: TA_ERR_HIP.  nq == 0 or
+ * nt == 0: TA_OK, the count zero, every nearest word all ones, every per-query count zero.
+ * The call enqueues its work on `stream` and returns without synchronising; the counter, nearest_dev and per_query_dev are initialised
+ * by kernels.  With every length bound known (strided sides, CSR max_len given on both) it is capturable under the rule above (run once
+ * outside the capture first); a CSR side with max_len = 0 costs one synchronisation to measure it.  ta_last_kernel_name names the kernel,
+ * ham_cross_kernel<NW> with NW = 4, 8 or 16 dwords per string. */
+#define TA_CROSS_UPPER 1u   /* only pairs with target index > query index (a set against itself: each unordered pair once, no (i, i)) */
+int ta_hamming_cross(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt,
+                     uint32_t k, uint32_t flags,
+                     ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                     uint64_t *nearest_dev    /* nq entries, or NULL */,
+                     uint32_t *per_query_dev  /* nq entries, or NULL */, void *stream);
+
 /* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
  * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
  * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of

@@ -413,6 +413,33 @@ def levenshtein_nearest_many(queries, targets, k, costs=LEVENSHTEIN_COSTS):
     return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32) for w in words]
 
 
+def hamming_cross_many(queries, targets, k, upper=False):
+    """Every query against every target in ONE device call (ta_hamming_cross): the sorted list of (q, t, d) with d =
+    hamming(queries[q], targets[t]) for every pair of equal length where that is at most k; upper = True keeps only the pairs with t > q
+    (a set against itself: each unordered pair once).  Queries of at most 64 bytes.  Both lists are uploaded; when there are more hits
+    than the first call's room, one more call runs with room for the count it reported."""
+    from . import batch as B
+    qs, ts = _cross_sides(queries, targets)
+    k = _k(k)
+    hits, count, _, _ = B.hamming_cross(qs, ts, k, upper=upper)
+    n = int(count.cpu()[0].item())
+    if n > hits.shape[0]:
+        hits, count, _, _ = B.hamming_cross(qs, ts, k, cap=n, upper=upper)
+    q, t, d = B.cross_to_arrays(hits, count)
+    return [(int(a), int(b), int(c)) for a, b, c in zip(q, t, d)]
+
+
+def hamming_nearest_many(queries, targets, k):
+    """For every query its nearest target within k mismatches and how many targets are within k, in ONE device call (ta_hamming_cross,
+    counting only): a list of (target, distance, n_hits) -- the smallest distance, at equal distance the lowest target index -- or None
+    where no target of the query's length is within k.  n_hits == 1 is the demultiplexer's "exactly one whitelist entry within k"."""
+    from . import batch as B
+    qs, ts = _cross_sides(queries, targets)
+    _, _, nearest, per_query = B.hamming_cross(qs, ts, _k(k), cap=0, nearest=True, per_query=True)
+    words, counts = nearest.cpu().numpy().view("uint64"), per_query.cpu().numpy().view("uint32")
+    return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32, int(c)) for w, c in zip(words, counts)]
+
+
 def levenshtein_select(a_len, b_len, k, costs=LEVENSHTEIN_COSTS):
     """The dispatcher arithmetic (src/levenshtein.rs:731-791): (max_k, unit_k, cell_bits, ref_lanes)."""
     s = _n.LevSelectC()

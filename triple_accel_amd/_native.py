@@ -36,8 +36,10 @@ ABI_SYMBOLS = [
     # search over a batch of (needle, haystack) pairs (ta_search_batch.hip)
     "ta_levenshtein_search_batch", "ta_hamming_search_batch",
     # every query against every target (ta_cross.hip)
-    "ta_levenshtein_cross",
+    "ta_levenshtein_cross", "ta_hamming_cross",
 ]
+
+TA_CROSS_UPPER = 1          # ta_hamming_cross flags: only pairs with target index > query index
 
 
 class EditCostsC(C.Structure):
@@ -191,6 +193,7 @@ def lib():
     sig("ta_levenshtein_search_batch", i32, [sp, sp, sz, u32, i32, cp, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     sig("ta_hamming_search_batch", i32, [sp, sp, sz, u32, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     sig("ta_levenshtein_cross", i32, [sp, sz, sp, sz, u32, cp, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p])
+    sig("ta_hamming_cross", i32, [sp, sz, sp, sz, u32, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p])
     _lib = L
     return L
 

@@ -510,6 +510,38 @@ def levenshtein_cross(queries: Strings, targets: Strings, k, costs=LEVENSHTEIN_C
     return hits, count, nearest
 
 
+def hamming_cross(queries: Strings, targets: Strings, k, cap=None, hits=None, count=None, nearest=False, per_query=False, upper=False):
+    """Every query against every target within k mismatches, on the device (ta_hamming_cross): -> (hits, count, nearest, per_query).  The
+    pair (q, t) is a hit with distance d exactly when both strings have the same length and hamming(query q, target t) = d <= k; strings
+    of different lengths are never a hit.  hits, count, nearest and cap are levenshtein_cross's (cross_to_arrays reads them).
+    per_query = True (or an int32 tensor of queries.n elements to reuse): per_query[q] = the number of hits of query q, whatever cap is;
+    else None.  upper = True keeps only the pairs with target index > query index, in every output: a set against itself gives each
+    unordered pair once.  Queries of at most 64 bytes.  Nothing is synchronised: read count before trusting hits."""
+    nq, nt, dev = queries.n, targets.n, targets.blob.device
+    if cap is None:
+        cap = hits.numel() // 4 if hits is not None else min(nq * nt, max(1024, 8 * max(nq, nt)))
+    hits = torch.empty((cap, 4), dtype=torch.int32, device=dev) if hits is None else hits
+    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+    if nearest is True:
+        nearest = torch.empty(nq, dtype=torch.int64, device=dev)
+    elif nearest is False:
+        nearest = None
+    if per_query is True:
+        per_query = torch.empty(nq, dtype=torch.int32, device=dev)
+    elif per_query is False:
+        per_query = None
+    assert hits.dtype == torch.int32 and hits.is_contiguous() and hits.numel() >= cap * 4
+    assert count.dtype == torch.int64 and count.numel() >= 1
+    assert nearest is None or (nearest.dtype == torch.int64 and nearest.is_contiguous() and nearest.numel() >= nq)
+    assert per_query is None or (per_query.dtype == torch.int32 and per_query.is_contiguous() and per_query.numel() >= nq)
+    rc = _n.lib().ta_hamming_cross(queries._ref(), nq, targets._ref(), nt, int(k), _n.TA_CROSS_UPPER if upper else 0,
+                                   hits.data_ptr() if cap else None, count.data_ptr(), cap,
+                                   None if nearest is None else nearest.data_ptr(), None if per_query is None else per_query.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return hits, count, nearest, per_query
+
+
 def cross_to_arrays(hits, count, allow_cut=False):
     """the device result of levenshtein_cross as numpy arrays (query, target, k), sorted by (query, target) (host copy).  More hits than
     the `cap` rows of `hits` were cut on the device (count says how many there are): that is an error here, not a silently shorter

@@ -1,5 +1,5 @@
-// ta_cross.hip -- ta_levenshtein_cross (include/triple_accel_amd.h): validation, the length bounds, the query tile and the
-// launch of lev_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
+// ta_cross.hip -- ta_levenshtein_cross and ta_hamming_cross (include/triple_accel_amd.h): validation, the length
+// bounds, the query tile and the launch of lev_cross.hip / ham_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
 // there is no synchronisation and the call can be captured into a graph.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -104,5 +104,52 @@ extern "C" int ta_levenshtein_cross(const ta_strings *queries, size_t nq, const 
     if ((rc = cross_fill64(count_dev, 0u, 1, st))) return rc;
     if (nearest_dev && (rc = cross_fill64((unsigned long long *)nearest_dev, 0xFFFFFFFFu, nq, st))) return rc;
     TA_HIP(lev_cross_launch(P, max_q <= 32 ? 1 : 2, trans, st));
+    return TA_OK;
+}
+
+extern "C" int ta_hamming_cross(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt,
+                                uint32_t k, uint32_t flags,
+                                ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                uint64_t *nearest_dev, uint32_t *per_query_dev, void *stream) {
+    if (!queries || !targets || !count_dev) { set_last_error_msg("null queries / targets / count_dev"); return TA_ERR_ARG; }
+    if (flags & ~TA_CROSS_UPPER) { set_last_error_msg("hamming cross: unknown flag bits"); return TA_ERR_ARG; }
+    if ((uint64_t)nq >> 32 || (uint64_t)nt >> 32) { set_last_error_msg("2^32 or more queries / targets"); return TA_ERR_ARG; }
+    if (nq && nt && (!queries->blob || !targets->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
+    if (cap && !hits_dev) { set_last_error_msg("cap > 0 with null hits_dev"); return TA_ERR_ARG; }
+    if (cap > SIZE_MAX / sizeof(ta_cross_hit)) { set_last_error_msg("cap * sizeof(ta_cross_hit) overflows"); return TA_ERR_ARG; }
+    if (cross_bound_known(queries) && cross_bound(queries) > 64) { set_last_error_msg("cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
+    if (cross_bound_known(targets) && cross_bound(targets) >> 32) { set_last_error_msg("cross: a target of 2^32 bytes or more"); return TA_ERR_UNSUPPORTED; }
+    if (!device_ready()) return TA_ERR_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard guard(st);
+    int rc;
+    if ((rc = cross_fill64(count_dev, 0u, 1, st))) return rc;
+    if (nearest_dev && (rc = cross_fill64((unsigned long long *)nearest_dev, 0xFFFFFFFFu, nq, st))) return rc;
+    if (per_query_dev && nq) TA_HIP(fill_u32_launch(per_query_dev, 0u, (uint32_t)nq, st));
+    if (nq == 0 || nt == 0) return TA_OK;
+    uint64_t max_q = 0, max_t = 0;
+    if ((rc = cross_max_lens(queries, (uint32_t)nq, targets, (uint32_t)nt, st, &max_q, &max_t))) return rc;
+    if (max_q > 64) { set_last_error_msg("cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
+    if (max_t >> 32) { set_last_error_msg("cross: a target of 2^32 bytes or more"); return TA_ERR_UNSUPPORTED; }
+
+    const int nw = max_q <= 16 ? 4 : max_q <= 32 ? 8 : 16;
+    const uint64_t chunk = 256u / (uint32_t)nw;                                    // queries staged at a time (ham_cross_body.h)
+    HamCrossParams P = {};
+    P.q = cross_view(queries); P.t = cross_view(targets);
+    P.nq = (uint32_t)nq; P.nt = (uint32_t)nt;
+    P.k8 = 8u * (k < 64u ? k : 64u) + 7u;                                          // (no string is longer than 64 bytes: k above that changes nothing)
+    P.upper = flags & TA_CROSS_UPPER;
+    P.hits = hits_dev; P.cap = cap; P.count = count_dev; P.nearest = (unsigned long long *)nearest_dev; P.per_query = per_query_dev;
+    // The query tile, as ta_levenshtein_cross sizes it: a wavefront loads its 64 targets once per tile, so a longer tile amortises them
+    // further and a shorter one makes more wavefronts.  About 16,384 wavefronts, whole staging chunks, at most 512 queries, and never
+    // more than 65,535 tiles (the grid's y dimension).
+    const uint64_t tgroups = ((uint64_t)nt + 63) / 64;
+    uint64_t qtile = (nq * tgroups + 16383) / 16384;
+    qtile = (qtile + chunk - 1) / chunk * chunk;
+    if (qtile > 512) qtile = 512;
+    if (const int f = env_int("TA_HCROSS_QTILE"); f > 0) qtile = (uint64_t)f;
+    if ((nq + qtile - 1) / qtile > 65535) qtile = (nq + 65534) / 65535;
+    P.qtile = (uint32_t)qtile;
+    TA_HIP(ham_cross_launch(P, nw, st));
     return TA_OK;
 }

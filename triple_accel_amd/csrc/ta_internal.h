@@ -247,6 +247,22 @@ struct CrossParams {
 constexpr uint32_t CROSS_MIN_QTILE = 16;
 hipError_t lev_cross_launch(const CrossParams &P, int nw, bool trans, hipStream_t st);
 
+// ta_hamming_cross (ham_cross.hip): one lane per target, kept in nw dwords of registers; a wavefront walks a tile of queries, staged
+// through LDS a chunk of 256 / nw at a time
+struct HamCrossParams {
+    StrView q, t;                 // queries (every one at most 4 nw bytes), targets
+    uint32_t nq, nt;
+    uint32_t k8;                  // 8 min(k, 64) + 7: the compare counts eight per mismatch
+    uint32_t upper;               // TA_CROSS_UPPER: only pairs with target index > query index
+    uint32_t qtile;               // queries per wavefront: ceil(nq / qtile) <= 65535
+    ta_cross_hit *hits;           // device: cap records, or nullptr with cap = 0
+    uint64_t cap;
+    unsigned long long *count;    // device, pre-zeroed
+    unsigned long long *nearest;  // device: nq words preset to all ones, or nullptr
+    uint32_t *per_query;          // device: nq words pre-zeroed, or nullptr
+};
+hipError_t ham_cross_launch(const HamCrossParams &P, int nw, hipStream_t st);
+
 // ta_multi.hip: the device set (one worker thread per entry).  multi_search_shards / multi_pair_shards: over how many of them a host
 // haystack / a host batch of that size is spread (1: the calling thread's own device path).  The search forms return the All-mode hits
 // sorted by end (best: only those with each shard's smallest k -- all the Best fold can keep), without the end == 0 match.
