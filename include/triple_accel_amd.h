@@ -224,7 +224,17 @@ void ta_thread_release(void);
 /* ---- batch API on device-resident data (new surface; N = 1 equals the single-call form) -- */
 
 /* String i of a batch is blob[off[i] .. off[i+1]) (CSR, n+1 offsets, device memory), or, when
- * off == NULL, blob[i*stride .. i*stride+len) (fixed length `len`, byte stride `stride`). */
+ * off == NULL, blob[i*stride .. i*stride+len) (fixed length `len`, byte stride `stride`).
+ * What the layout may be (tests/test_gpu_layouts.py holds every device entry to it, on every kernel route):
+ *   - `blob` may have any byte alignment, and may point into the middle of an allocation;
+ *   - `stride` and `len` are independent: stride > len leaves gaps between the strings, stride < len makes the strings overlapping
+ *     windows of one sequence; stride = 0 is ONE string shared by every pair (documented for the needles of the two *_search_batch
+ *     entries; the other entries then compare that one string n times);
+ *   - CSR offsets need not start at 0 and `off` may point into the middle of a larger batch's offsets: only off[0 .. n] are read, and
+ *     only blob[off[0] .. off[n]) belongs to the batch;
+ *   - the bytes that belong to no string -- in front of the blob, in the gaps of the strided form, the TA_BLOB_SLACK bytes behind the
+ *     last string -- must be READABLE where the slack rule says so; what they hold is irrelevant to every answer;
+ *   - outputs are written at the documented slots only: nothing in front of out[0], nothing behind the last slot. */
 typedef struct {
     const uint8_t *blob;     /* device */
     const uint64_t *off;     /* device, n+1 entries, or NULL for the strided form */
