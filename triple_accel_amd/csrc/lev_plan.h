@@ -1,4 +1,5 @@
-// lev_plan.h -- host-side launch planning for the band-wavefront kernel (lev_band_body.h).
+// lev_plan.h -- host-side launch planning for the band-wavefront kernel (lev_band_body.h), and the pure host rules every entry point
+// shares (cost validity, the unit-cost families and their multiples, the length-order threshold, the cross entries' query tile).
 // Pure integer logic, shared by the product's C ABI (ta_api.hip) and the test-only emulation.
 #pragma once
 #include <stddef.h>
@@ -21,6 +22,30 @@ struct LevPlan {
 };
 
 static inline uint32_t lev_sat_sub(uint32_t a, uint32_t b) { return a > b ? a - b : 0u; }
+
+// ---- the host rules every entry point shares, stated once (the C-ABI files call them through the ta_edit_costs wrappers of ta_internal.h)
+// EditCosts::new's three assertions (src/levenshtein.rs:44-52)
+static inline bool lev_costs_valid(uint32_t mc, uint32_t gc, bool has_t, uint32_t tc) {
+    return mc > 0 && gc > 0 && (!has_t || (tc > 0 && (tc >> 1) < mc && (tc >> 1) < gc));
+}
+// the unit-cost families: LEVENSHTEIN_COSTS / RDAMERAU_COSTS (src/levenshtein.rs:79-91)
+static inline bool lev_is_unit(uint32_t mc, uint32_t gc, uint32_t sg, bool has_t, uint32_t tc) {
+    return mc == 1 && gc == 1 && sg == 0 && (!has_t || tc == 1);
+}
+// ragged (CSR) batches of this size take their pairs in length order (util_kernels.hip: length_order_launch)
+static inline bool lev_wants_length_order(bool any_csr, uint64_t n, uint64_t max_len) { return any_csr && n >= 4096 && max_len >= 16; }
+// Queries per wavefront of the cross entries (ta_cross.hip): about 16,384 wavefronts (8 per SIMD of 256 CUs, twice over), at least
+// min_tile, whole multiples of round_to, at most 512, `forced` (> 0: a tuning switch) as it is, and never more than 65,535 tiles (the
+// grid's y dimension).  Levenshtein: (CROSS_MIN_QTILE, 1); Hamming: (0, its staging chunk).
+static inline uint32_t cross_qtile(uint64_t nq, uint64_t nt, uint32_t min_tile, uint32_t round_to, int forced) {
+    uint64_t qtile = (nq * ((nt + 63) / 64) + 16383) / 16384;
+    if (qtile < min_tile) qtile = min_tile;
+    qtile = (qtile + round_to - 1) / round_to * round_to;
+    if (qtile > 512) qtile = 512;
+    if (forced > 0) qtile = (uint64_t)forced;
+    if ((nq + qtile - 1) / qtile > 65535) qtile = (nq + 65534) / 65535;
+    return (uint32_t)qtile;
+}
 
 // The band.  An alignment of cost <= K that strays t diagonals outside [min(0,delta), max(0,delta)]
 // (delta = b_len - a_len) pays for at least 2t + |delta| gap characters and one gap opening, so
@@ -95,6 +120,11 @@ static inline LevPlan lev_make_plan(uint32_t k, uint32_t mc, uint32_t gc, uint32
 static inline uint32_t lev_unit_scale(uint32_t mc, uint32_t gc, uint32_t sg, bool has_t, uint32_t tc) {
     return (sg == 0 && mc == gc && gc >= 2 && (!has_t || tc == gc)) ? gc : 0u;
 }
+// 1 for the unit-cost families, g for their multiples, 0 otherwise: "the unit-cost kernels answer these costs".  Not lev_unit_scale: the
+// passes that recurse on g != 0 with k / g and unit costs (lev_pass, ta_levenshtein_trace_batch) would recurse for ever on a 1.
+static inline uint32_t lev_cost_scale(uint32_t mc, uint32_t gc, uint32_t sg, bool has_t, uint32_t tc) {
+    return lev_is_unit(mc, gc, sg, has_t, tc) ? 1u : lev_unit_scale(mc, gc, sg, has_t, tc);
+}
 
 // ---- bit-parallel band kernel (lev_bits_body.h): unit costs only, one pair per lane, window of 4*NA diagonals
 static const int LEV_BITS_MAX_NA = 32;      // kernels exist for NA = 1..16 and the even NA up to 32
@@ -114,7 +144,7 @@ struct LevBitsPlan {
 static inline LevBitsPlan lev_bits_make_plan(uint32_t k, uint32_t mc, uint32_t gc, uint32_t sg, bool has_t, uint32_t tc,
                                              uint64_t max_len, int force_NA = 0, int force_ch = 0, int force_static = 0) {
     LevBitsPlan p;
-    p.ok = mc == 1 && gc == 1 && sg == 0 && (!has_t || tc == 1);   // LEVENSHTEIN_COSTS / RDAMERAU_COSTS (src/levenshtein.rs:79-91)
+    p.ok = lev_is_unit(mc, gc, sg, has_t, tc);   // LEVENSHTEIN_COSTS / RDAMERAU_COSTS (src/levenshtein.rs:79-91)
     p.u = lev_batch_unit_k(k, mc, gc, sg, max_len);
     const uint64_t w = (uint64_t)p.u + 1u + (has_t ? 2u : 0u);     // the transposition test looks one row past each band edge
     uint64_t na = (w + 3) / 4, na_st = (w + 3 + 3) / 4;            // the static form gives up 3 window bits
@@ -156,7 +186,7 @@ static inline LevBits2Plan lev_bits2_make_plan(uint32_t k, uint32_t mc, uint32_t
     LevBits2Plan p;
     p.u = lev_batch_unit_k(k, mc, gc, sg, max_len);
     const uint64_t w = (uint64_t)p.u + 1u + (has_t ? 2u : 0u);
-    p.ok = mc == 1 && gc == 1 && sg == 0 && (!has_t || tc == 1) && fixed_length && w <= 15 && max_len <= 65000 && max_len >= 1 &&
+    p.ok = lev_is_unit(mc, gc, sg, has_t, tc) && fixed_length && w <= 15 && max_len <= 65000 && max_len >= 1 &&
            pairs >= LEV_BITS2_MIN_PAIRS;
     p.NA = 8;                                                  // the stride-8 window: 8 registers of 2 + 2 bytes
     p.Tw = (p.u + (has_t ? 1u : 0u) + 2u + 63u) & ~63u;        // (the stream of `a` runs two iterations ahead of the window's last row)
@@ -178,7 +208,7 @@ static inline bool lev_bitsq_applies(uint32_t k, uint32_t mc, uint32_t gc, uint3
                                      bool fixed_length, uint64_t pairs, uint32_t *u_out) {
     const uint32_t u = lev_batch_unit_k(k, mc, gc, sg, max_len);
     if (u_out) *u_out = u;
-    return mc == 1 && gc == 1 && sg == 0 && (!has_t || tc == 1) && fixed_length && (uint64_t)u + 1u + (has_t ? 2u : 0u) <= 33u &&
+    return lev_is_unit(mc, gc, sg, has_t, tc) && fixed_length && (uint64_t)u + 1u + (has_t ? 2u : 0u) <= 33u &&
            max_len >= 1 && max_len <= 0x7FFFFF00ull && pairs >= LEV_BITSQ_MIN_PAIRS;
 }
 
@@ -233,7 +263,7 @@ static inline bool lev_bitsqw_hash(const uint8_t *sym, size_t n, uint32_t *shift
 static inline bool lev_one_applies(uint32_t k, uint32_t mc, uint32_t gc, uint32_t sg, bool has_t, uint32_t tc, uint64_t max_len, uint32_t *u_out) {
     const uint32_t u = lev_batch_unit_k(k, mc, gc, sg, max_len);
     if (u_out) *u_out = u;
-    return mc == 1 && gc == 1 && sg == 0 && (!has_t || tc == 1) && (uint64_t)u + 1u + (has_t ? 2u : 0u) <= 64u && max_len <= 32000u;
+    return lev_is_unit(mc, gc, sg, has_t, tc) && (uint64_t)u + 1u + (has_t ? 2u : 0u) <= 64u && max_len <= 32000u;
 }
 
 // ---- which kernel runs a k-bounded pass, and roughly what it costs (wave-instructions per pair; only ratios matter)
@@ -255,7 +285,7 @@ static inline LevChoice lev_choose(uint32_t k, uint32_t mc, uint32_t gc, uint32_
     const bool latency = pairs <= LEV_LATENCY_PAIRS;
     const LevBitsPlan bp = lev_bits_make_plan(k, mc, gc, sg, has_t, tc, max_len);
     const LevPlan pl = lev_make_plan(k, mc, gc, sg, max_len, 0, 0);
-    const bool unit = mc == 1 && gc == 1 && sg == 0 && (!has_t || tc == 1);
+    const bool unit = lev_is_unit(mc, gc, sg, has_t, tc);
     LevChoice c;
     if (bp.ok && !dp_only) {                                   // one pair per lane, ~6 instructions per window dword + 25
         c.kernel = LEV_K_BITS; c.rows_per_lane = 0;

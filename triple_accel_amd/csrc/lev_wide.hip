@@ -296,7 +296,7 @@ hipError_t lev_wide_launch(const LevParams &P, bool trans, hipStream_t s, uint32
     WideScratch S;
     S.line = (uint64_t)P.lds_per_wave;
     // boundary scratch (only touched when a string spans more than one stripe)
-    Scratch &sc = tls_scratch(6);
+    Scratch &sc = tls_scratch(SLOT_LINES);
     if (sc.ensure((size_t)grid * 6 * S.line * sizeof(uint32_t)) != TA_OK) return hipErrorOutOfMemory;
     S.buf = (uint32_t *)sc.dev;
     const bool affine = P.sg > 0;
@@ -312,7 +312,7 @@ hipError_t lev_wide_launch(const LevParams &P, bool trans, hipStream_t s, uint32
 hipError_t lev_wide_trace_launch(const LevParams &P, bool trans, hipStream_t s) {
     WideScratch S;
     S.line = (uint64_t)P.lds_per_wave;
-    Scratch &sc = tls_scratch(6);
+    Scratch &sc = tls_scratch(SLOT_LINES);
     if (sc.ensure((size_t)6 * S.line * sizeof(uint32_t)) != TA_OK) return hipErrorOutOfMemory;
     S.buf = (uint32_t *)sc.dev;
     const bool affine = P.sg > 0;
@@ -336,7 +336,7 @@ hipError_t lev_wide_u32_launch(const LevParams &P, bool trans, bool trace, hipSt
     if (grid == 0) return hipSuccess;
     WideScratch S;
     S.line = (uint64_t)P.lds_per_wave;
-    Scratch &sc = tls_scratch(6);
+    Scratch &sc = tls_scratch(SLOT_LINES);
     if (sc.ensure((size_t)grid * 6 * S.line * sizeof(uint32_t)) != TA_OK) return hipErrorOutOfMemory;
     S.buf = (uint32_t *)sc.dev;
     const bool affine = P.sg > 0;

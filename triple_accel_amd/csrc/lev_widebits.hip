@@ -39,7 +39,7 @@ hipError_t lev_widebits_launch(const LevParams &P0, int rows_per_lane, uint64_t 
         P.bnd_line = max_len + 66;
         const uint64_t per_wave = 6ull * P.bnd_line * sizeof(uint32_t), budget = 8ull << 30;
         if ((uint64_t)grid * per_wave > budget) grid = (uint32_t)(budget / per_wave ? budget / per_wave : 1);
-        Scratch &sc = tls_scratch(6);
+        Scratch &sc = tls_scratch(SLOT_LINES);
         if (sc.ensure((size_t)grid * per_wave) != TA_OK) return hipErrorOutOfMemory;
         P.bnd = (uint32_t *)sc.dev;
     }
@@ -87,7 +87,7 @@ static hipError_t huge_launch_t(const uint8_t *ap, const uint8_t *bp, uint32_t n
     if (const char *e = env_str("TA_WB_TILE_STEPS")) { long v = atol(e); if (v >= 64) cb = (uint64_t)v & ~(uint64_t)63; }
     H.CB = (uint32_t)cb;
     H.line = (uint64_t)m + 66;
-    Scratch &ls = tls_scratch(6), &ss = tls_scratch(8);    // (slots 4 and 5 hold the exp loop's subsets while this runs)
+    Scratch &ls = tls_scratch(SLOT_LINES), &ss = tls_scratch(SLOT_AUX_B);    // (who else uses them, and when: ScratchSlot, ta_internal.h)
     if (ls.ensure((size_t)stripes * 3 * H.line * sizeof(uint32_t)) != TA_OK) return hipErrorOutOfMemory;
     if (ss.ensure((size_t)stripes * 64 * 16 * sizeof(uint32_t)) != TA_OK) return hipErrorOutOfMemory;
     H.lines = (uint32_t *)ls.dev; H.state = (uint32_t *)ss.dev;

@@ -1,5 +1,8 @@
 // ta_api.hip -- the C ABI (include/triple_accel_amd.h): validation, launch planning, staging.
 // No CPU fallback lives here: every compute entry point needs a HIP device.
+// The host rules the other C-ABI files share are defined here once (declared in ta_internal.h: measure_max_lens, order_pairs,
+// check_batch_args; the scratch slots are named by its ScratchSlot); the pure ones -- cost checks, unit-cost tests, the length-order
+// threshold, the cross entries' query tile -- are in lev_plan.h.
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -74,7 +77,7 @@ void Scratch::release() {
     dev = nullptr; cap = 0;
 }
 Scratch::~Scratch() { /* at thread exit the HIP runtime may already be gone (process teardown): ta_thread_release() is the explicit way */ }
-Scratch &tls_scratch(int which) {
+Scratch &tls_scratch(ScratchSlot which) {
     static thread_local Scratch s[TA_SCRATCH_SLOTS];
     return s[which];
 }
@@ -167,24 +170,11 @@ bool early_out_enabled() { return g_opt_early_out || env_int("TA_EARLY_OUT"); }
 static thread_local bool g_opt_unit_prefilter = false;
 bool unit_prefilter_enabled() { return g_opt_unit_prefilter || env_int("TA_UNIT_PREFILTER"); }
 
-static bool costs_ok(const ta_edit_costs *c) {   // EditCosts::new, src/levenshtein.rs:44-52
-    if (!c) return false;
-    if (!(c->mismatch_cost > 0) || !(c->gap_cost > 0)) return false;
-    if (c->has_transpose) {
-        if (!(c->transpose_cost > 0)) return false;
-        if (!((c->transpose_cost >> 1) < c->mismatch_cost)) return false;
-        if (!((c->transpose_cost >> 1) < c->gap_cost)) return false;
-    }
-    return true;
-}
-
-static StrView view_of(const ta_strings *s) { return StrView{s->blob, s->off, s->stride, s->len}; }
-
 // longest string of a batch side: given, implied (strided) or measured on the device
 static int side_max_len(const ta_strings *s, uint32_t n, hipStream_t st, uint64_t *out) {
     if (!s->off) { *out = s->len; return TA_OK; }
     if (s->max_len) { *out = s->max_len; return TA_OK; }
-    Scratch &sc = tls_scratch(3);
+    Scratch &sc = tls_scratch(SLOT_COUNT);
     int rc = sc.ensure(16);
     if (rc) return rc;
     TA_HIP(hipMemsetAsync(sc.dev, 0, 4, st));
@@ -245,7 +235,7 @@ static int lev_pass(const ta_strings *a, const ta_strings *b, uint32_t n_work, c
     const bool pinned = env_int("TA_NO_LATENCY_RULE") || env_int("TA_FORCE_NA") || env_int("TA_BITS_STATIC") || env_int("TA_FORCE_CH") ||
                         env_int("TA_FORCE_SLICED");
     LevChoice ch = lev_choose(k, c->mismatch_cost, gc, sg, trans, tcost, max_len, dp_forced, pinned ? 0xFFFFFFFFu : n_work);
-    const bool unit = c->mismatch_cost == 1 && gc == 1 && sg == 0 && (!trans || tcost == 1);
+    const bool unit = costs_unit(c);
     // a handful of long fixed-length pairs: the tiled row-blocked form uses many wavefronts per pair, whatever the band
     if (unit && !dp_forced && ch.kernel != LEV_K_BITS && (n_work == 1 || (n_work <= 16 && !subset)) && !a->off && !b->off &&
         (a->len < b->len ? a->len : b->len) > 2ull * 4096ull && !env_int("TA_WB_NO_TILES")) {
@@ -343,22 +333,40 @@ static int lev_pass(const ta_strings *a, const ta_strings *b, uint32_t n_work, c
     return TA_OK;
 }
 
-// The pairs of a ragged batch in length order (util_kernels.hip: length_order_launch) into thread-local scratch; *order_out = the list.
-// The histogram scratch must be zero on entry and every complete pass leaves it zero: `clean` says the last pass of this thread was
-// complete -- after one that failed midway the histogram is zeroed again instead of trusted.
-static int order_pairs(const ta_strings *a, const ta_strings *b, uint32_t n, uint32_t u, uint64_t max_len, bool by_steps, bool exact,
-                       hipStream_t st, const uint32_t **order_out, bool *exact_columns) {
-    static thread_local bool clean = false;
-    Scratch &ord = tls_scratch(13), &bins = tls_scratch(14);
+// (ta_internal.h) every fill of a capturable call is a kernel, never a memset node: DESIGN.md 3.2f
+int order_pairs(const ta_strings *a, const ta_strings *b, uint32_t n, uint32_t u, uint64_t max_len, bool by_steps, bool exact,
+                ScratchSlot order_slot, ScratchSlot bins_slot, hipStream_t st, const uint32_t **order_out, bool *exact_columns) {
+    Scratch &ord = tls_scratch(order_slot), &bins = tls_scratch(bins_slot);
     constexpr size_t BINS_BYTES = 2 * 1024 * 32 * 4;                    // histogram + cursors: 1024 bins x 32 counters each
-    const bool fresh = bins.cap < BINS_BYTES || !clean;
+    const bool fresh = bins.cap < BINS_BYTES || !bins.bins_clean;
     int rc;
     if ((rc = ord.ensure((size_t)n * 4)) || (rc = bins.ensure(BINS_BYTES))) return rc;
-    if (fresh) TA_HIP(hipMemsetAsync(bins.dev, 0, BINS_BYTES / 2, st));
-    clean = false;
+    if (fresh) TA_HIP(fill_u32_launch((uint32_t *)bins.dev, 0u, (uint32_t)(BINS_BYTES / 8), st));
+    bins.bins_clean = false;
     TA_HIP(length_order_launch(view_of(a), view_of(b), nullptr, n, u, max_len, by_steps, (uint32_t *)bins.dev, (uint32_t *)ord.dev, st, exact, exact_columns));
-    clean = true;
+    bins.bins_clean = true;
     *order_out = (const uint32_t *)ord.dev;
+    return TA_OK;
+}
+
+int measure_max_lens(const ta_strings *a, uint32_t na, const ta_strings *b, uint32_t nb, unsigned long long *dst, hipStream_t st,
+                     uint64_t *ma, uint64_t *mb) {
+    *ma = side_bound(a);
+    *mb = side_bound(b);
+    const bool need_a = !side_bound_known(a), need_b = !side_bound_known(b);
+    if (!need_a && !need_b) return TA_OK;
+    TA_HIP(fill_u32_launch((uint32_t *)dst, 0u, 4, st));
+    const StrView none = {nullptr, nullptr, 0, 0};
+    if (need_a && need_b && na == nb) TA_HIP(search_batch_maxlen_launch(view_of(a), view_of(b), na, dst, st));   // pair batches: one launch
+    else {
+        if (need_a) TA_HIP(search_batch_maxlen_launch(view_of(a), none, na, dst, st));
+        if (need_b) TA_HIP(search_batch_maxlen_launch(none, view_of(b), nb, dst, st));
+    }
+    unsigned long long host[2] = {0, 0};
+    TA_HIP(hipMemcpyAsync(host, dst, 16, hipMemcpyDeviceToHost, st));
+    TA_HIP(hipStreamSynchronize(st));
+    if (need_a) *ma = host[0];
+    if (need_b) *mb = host[1];
     return TA_OK;
 }
 
@@ -372,9 +380,9 @@ static int batch_max_len(const ta_strings *a, const ta_strings *b, uint32_t n, h
     return TA_OK;
 }
 
-static int check_batch_args(const ta_strings *a, const ta_strings *b, size_t n, const void *out) {
+int check_batch_args(const void *a, const void *b, const void *a_data, const void *b_data, size_t n, const void *out, const char *what) {
     if (!a || !b || (!out && n) || n > 0xFFFFFFF0ull) { set_last_error_msg("bad batch arguments"); return TA_ERR_ARG; }
-    if (n && (!a->blob || !b->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
+    if (n && (!a_data || !b_data)) { set_last_error_msg(what); return TA_ERR_ARG; }
     return TA_OK;
 }
 
@@ -474,7 +482,7 @@ void ta_free(void *p) { free(p); }
  * runtime may already be gone by then). */
 void ta_thread_release(void) {
     (void)hipDeviceSynchronize();
-    for (int i = 0; i < TA_SCRATCH_SLOTS; i++) tls_scratch(i).release();
+    for (int i = 0; i < TA_SCRATCH_SLOTS; i++) tls_scratch((ScratchSlot)i).release();
     call_ctx().release();
     search_report_box().release();
     search_resident_reset();
@@ -502,16 +510,14 @@ int ta_levenshtein_k_batch(const ta_strings *a, const ta_strings *b, size_t n, u
     // every wavefront then sees pairs within 8 bytes of each other.  TA_NO_LENGTH_ORDER=1 keeps the batch order.
     const uint32_t *order = nullptr;
     bool exact_columns = false;
-    if ((a->off || b->off) && n >= 4096 && max_len >= 16 && !env_int("TA_NO_LENGTH_ORDER")) {
+    if (lev_wants_length_order(a->off || b->off, n, max_len) && !env_int("TA_NO_LENGTH_ORDER")) {
         const uint32_t u = lev_batch_unit_k(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, max_len);
         // the key counts what the kernel of this pass iterates over: columns (bit-parallel kernels) or anti-diagonal steps (DP band kernel).
         // (the kernels whose time follows max(len_a, len_b) or len_a -- two pairs per lane, the single-pair kernel, the row-blocked
         // one -- never see a length-ordered CSR wavefront of many pairs: the first takes fixed-length batches only, the other two run ONE pair
         // per wavefront, where the order only shapes the launch's tail; len_b is the right key for everything that is ordered by columns.)
-        const bool unit = (costs->mismatch_cost == 1 && costs->gap_cost == 1 && costs->start_gap_cost == 0 && (!costs->has_transpose || costs->transpose_cost == 1)) ||
-                          lev_unit_scale(costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose != 0, costs->transpose_cost);
-        const bool by_steps = !unit || env_int("TA_NO_BITS") || env_int("TA_FORCE_D") || env_int("TA_FORCE_L");
-        if ((rc = order_pairs(a, b, (uint32_t)n, u, max_len, by_steps, env_int("TA_BITS_VLINE") != 0, st, &order, &exact_columns))) return rc;
+        const bool by_steps = !costs_scale(costs) || env_int("TA_NO_BITS") || env_int("TA_FORCE_D") || env_int("TA_FORCE_L");
+        if ((rc = order_pairs(a, b, (uint32_t)n, u, max_len, by_steps, env_int("TA_BITS_VLINE") != 0, SLOT_ORDER, SLOT_ORDER_BINS, st, &order, &exact_columns))) return rc;
     }
     // TA_OPT_UNIT_PREFILTER (an option, off by default: the work then depends on the data): a weighted batch first runs the UNIT-cost
     // bit-parallel band pass with k' = lev_unit_filter_k -- "unit distance > k'" implies "weighted distance > k", i.e. None
@@ -519,12 +525,10 @@ int ta_levenshtein_k_batch(const ta_strings *a, const ta_strings *b, size_t n, u
     // device).  Dissimilar batches cost the unit pass alone; a batch of near pairs pays for both.
     if (unit_prefilter_enabled() && n >= 1024 && !env_int("TA_NO_BITS") && !env_int("TA_FORCE_D") && !env_int("TA_FORCE_L")) {
         const bool trans = costs->has_transpose != 0;
-        const bool unit_family = (costs->mismatch_cost == 1 && costs->gap_cost == 1 && costs->start_gap_cost == 0 && (!trans || costs->transpose_cost == 1)) ||
-                                 lev_unit_scale(costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, trans, costs->transpose_cost);
         const uint32_t kf = lev_unit_filter_k(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, trans, costs->transpose_cost);
-        if (!unit_family && kf != 0xFFFFFFFFu && lev_choose(kf, 1, 1, 0, trans, trans ? 1u : 0u, max_len, false, (uint32_t)n).kernel == LEV_K_BITS) {
+        if (!costs_scale(costs) && kf != 0xFFFFFFFFu && lev_choose(kf, 1, 1, 0, trans, trans ? 1u : 0u, max_len, false, (uint32_t)n).kernel == LEV_K_BITS) {
             const ta_edit_costs uc = {1, 1, 0, (uint8_t)(trans ? 1 : 0), (uint8_t)(trans ? 1 : 0)};
-            Scratch &lst = tls_scratch(4), &cnt = tls_scratch(3);
+            Scratch &lst = tls_scratch(SLOT_SUBSET_A), &cnt = tls_scratch(SLOT_COUNT);
             if ((rc = lst.ensure(n * 4)) || (rc = cnt.ensure(16))) return rc;
             if ((rc = lev_pass(a, b, (uint32_t)n, order, kf, &uc, max_len, out_dev, st, false))) return rc;
             TA_HIP(fill_u32_launch((uint32_t *)cnt.dev, 0u, 1, st));
@@ -577,7 +581,7 @@ int ta_levenshtein_k_batch_alphabet(const ta_strings *a, const ta_strings *b, si
     }
     hipStream_t st = (hipStream_t)stream;
     StreamGuard guard(st);
-    Scratch &bad = tls_scratch(15), &cnt = tls_scratch(16);
+    Scratch &bad = tls_scratch(SLOT_ALPHA_BAD), &cnt = tls_scratch(SLOT_ALPHA_COUNT);
     // two counters taken in turn: this pass appends to one and zeroes the other for the next pass (no fill per call; both are
     // zeroed once, when the scratch is allocated)
     // (`clean`: the last pass of this thread ran to its last launch -- the counter it left behind is zero.  A pass that failed midway leaves
@@ -638,7 +642,7 @@ int ta_levenshtein_exp_batch(const ta_strings *a, const ta_strings *b, size_t n,
     rc = batch_max_len(a, b, (uint32_t)n, st, &max_len);
     if (rc) return rc;
     // subset ping-pong buffers + counter
-    Scratch &s0 = tls_scratch(4), &s1 = tls_scratch(5), &cnt = tls_scratch(3), &bnd = tls_scratch(10), &wrk = tls_scratch(11);
+    Scratch &s0 = tls_scratch(SLOT_SUBSET_A), &s1 = tls_scratch(SLOT_SUBSET_B), &cnt = tls_scratch(SLOT_COUNT), &bnd = tls_scratch(SLOT_EXP_BOUND), &wrk = tls_scratch(SLOT_EXP_WORK);
     if ((rc = s0.ensure(n * 4)) || (rc = s1.ensure(n * 4)) || (rc = cnt.ensure(16))) return rc;
     // Bag lower bound per pair (util_kernels.hip): a doubling round only takes the unresolved pairs whose bound admits its
     // threshold -- the others could only return None from it.  Same return values, fewer rounds for dissimilar strings.
@@ -663,12 +667,10 @@ int ta_levenshtein_exp_batch(const ta_strings *a, const ta_strings *b, size_t n,
     k = k_first;
     // ragged (CSR) batches: the rounds take their pairs in length order, as ta_levenshtein_k_batch does (the list of the still
     // unresolved pairs is compacted from the ordered one, which keeps it ordered block by block)
-    if ((a->off || b->off) && n >= 4096 && max_len >= 16 && !env_int("TA_NO_LENGTH_ORDER")) {
+    if (lev_wants_length_order(a->off || b->off, n, max_len) && !env_int("TA_NO_LENGTH_ORDER")) {
         const uint32_t u0 = lev_batch_unit_k(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, max_len);
-        const bool unit = (costs->mismatch_cost == 1 && costs->gap_cost == 1 && costs->start_gap_cost == 0 && (!costs->has_transpose || costs->transpose_cost == 1)) ||
-                          lev_unit_scale(costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose != 0, costs->transpose_cost);
         const uint32_t *ordered = nullptr;
-        if ((rc = order_pairs(a, b, (uint32_t)n, u0, max_len, !unit || env_int("TA_NO_BITS"), false, st, &ordered, nullptr))) return rc;
+        if ((rc = order_pairs(a, b, (uint32_t)n, u0, max_len, !costs_scale(costs) || env_int("TA_NO_BITS"), false, SLOT_ORDER, SLOT_ORDER_BINS, st, &ordered, nullptr))) return rc;
         sub_in = (uint32_t *)ordered;
     }
     int flip = 0;
@@ -893,7 +895,7 @@ static int stage_pair(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b
         *S->out_host = TA_SLOT_EMPTY;
         return TA_OK;
     }
-    Scratch &sc = tls_scratch(0);
+    Scratch &sc = tls_scratch(SLOT_PAIR_STAGE);
     if ((rc = sc.ensure(a_pad + b_pad + 256))) return rc;
     uint8_t *base = (uint8_t *)sc.dev;
     if (a_len) TA_HIP(hipMemcpyAsync(base, a, a_len, hipMemcpyHostToDevice, cx.st));
@@ -977,7 +979,7 @@ static int trace_widebits(const uint8_t *x, size_t n, const uint8_t *y, size_t m
     ta_strings &sa = S.sa, &sb = S.sb;
     uint32_t *od = S.out_dev;
     hipStream_t tst = S.st;
-    Scratch &ts = tls_scratch(9), &bl = tls_scratch(6);
+    Scratch &ts = tls_scratch(SLOT_TRACE), &bl = tls_scratch(SLOT_LINES);
     if ((rc = ts.ensure((size_t)rec_words * 4)) || (rc = bl.ensure((size_t)6 * (m + 66) * 4))) return rc;
     LevParams P;
     P.a = view_of(&sa); P.b = view_of(&sb);
@@ -1027,7 +1029,7 @@ static int trace_wide(const uint8_t *x, size_t n, const uint8_t *y, size_t m, bo
     ta_strings &sa = S.sa, &sb = S.sb;
     uint32_t *od = S.out_dev;
     hipStream_t tst = S.st;
-    Scratch &ts = tls_scratch(9);
+    Scratch &ts = tls_scratch(SLOT_TRACE);
     if ((rc = ts.ensure((size_t)code_words * 4))) return rc;
     LevParams P;
     P.a = view_of(&sa); P.b = view_of(&sb);
@@ -1094,12 +1096,12 @@ static int trace_bits_batch(const ta_strings *a, const ta_strings *b, size_t n, 
     // CSR batches: both kernels run a wavefront to the longest of its 64 pairs -- the pairs are taken in length order (as
     // ta_levenshtein_k_batch takes them), the same list for the distance pass and the trace kernel.  TA_NO_LENGTH_ORDER=1 keeps the batch order.
     const uint32_t *order = nullptr;
-    if (!fixed && n >= 4096 && max_len >= 16 && !env_int("TA_NO_LENGTH_ORDER") &&
-        (rc = order_pairs(a, b, (uint32_t)n, u, max_len, false, false, st, &order, nullptr))) return rc;
+    if (lev_wants_length_order(!fixed, n, max_len) && !env_int("TA_NO_LENGTH_ORDER") &&
+        (rc = order_pairs(a, b, (uint32_t)n, u, max_len, false, false, SLOT_ORDER, SLOT_ORDER_BINS, st, &order, nullptr))) return rc;
     if (!fold && (rc = lev_pass(a, b, (uint32_t)n, order, k, costs, max_len, out_dev, st))) return rc;
     // (a script of cost <= u has at most 2 u + 1 runs, and never more than n + m)
     uint32_t runs_cap = (uint32_t)(2 * max_len + 1 < 2ull * u + 2 ? 2 * max_len + 1 : 2ull * u + 2);
-    Scratch &cs = tls_scratch(9), &ps = tls_scratch(8), &ss = tls_scratch(7);
+    Scratch &cs = tls_scratch(SLOT_TRACE), &ps = tls_scratch(SLOT_AUX_B), &ss = tls_scratch(SLOT_AUX_A);
     if ((rc = cs.ensure((size_t)waves * tiles * lev_bits_trace_ckpt_words(trans) * 64u * 4u)) || (!packed && (rc = ps.ensure((size_t)n * runs_cap * 4u))) ||
         (rc = ss.ensure((size_t)n * 4u))) return rc;
     LevBitsTraceParams T;
@@ -1152,7 +1154,7 @@ int ta_levenshtein_trace(const uint8_t *a, size_t a_len, const uint8_t *b, size_
     if (!pl.ok) pl = lev_make_plan(sel.max_k, costs->mismatch_cost, gc, sg, m, 66, 0);
     if (!pl.ok) {
         // band too wide for the register kernel: the unit-cost families take the row-blocked bit-parallel kernel with records
-        const bool unit = costs->mismatch_cost == 1 && gc == 1 && sg == 0 && (!costs->has_transpose || costs->transpose_cost == 1);
+        const bool unit = costs_unit(costs);
         const uint64_t stripes = (n + 4095) / 4096, tcols = (uint64_t)m + 64;
         const uint64_t rec_words = stripes * tcols * 64ull * 6ull;
         const uint64_t code_words = ((n + 2047) / 2048) * tcols * 64ull * 2ull;           // DP wide kernel: 2 bits per cell
@@ -1172,7 +1174,7 @@ int ta_levenshtein_trace(const uint8_t *a, size_t a_len, const uint8_t *b, size_
     const uint32_t tw = (uint32_t)lev_trace_words(pl.D);
     const size_t taus = (n + m + 1) / 2 + 1;
     const size_t trace_words = taus * 2 * 64 * tw;
-    Scratch &ts = tls_scratch(6);
+    Scratch &ts = tls_scratch(SLOT_LINES);
     if ((rc = ts.ensure(trace_words * 4))) return rc;
     LevParams P;
     P.a = view_of(&sa); P.b = view_of(&sb);
@@ -1277,9 +1279,8 @@ static int trace_batch_impl(const ta_strings *a, const ta_strings *b, size_t n, 
     // strings' bytes instead of 21 x.  TA_TRACE_NO_BITS=1 keeps the DP band kernel's records for these cost sets too.
     {
         const bool trans = costs->has_transpose != 0;
-        const bool unit = costs->mismatch_cost == 1 && gc == 1 && sg == 0 && (!trans || costs->transpose_cost == 1);
         const uint32_t u = lev_batch_unit_k(k, 1, 1, 0, max_len);
-        if (unit && (uint64_t)u + 1u + (trans ? 2u : 0u) <= 33u && max_len < (1ull << 29) /* a run's count has 29 bits */ && !env_int("TA_TRACE_NO_BITS") && !env_int("TA_NO_BITS")) {
+        if (costs_unit(costs) && (uint64_t)u + 1u + (trans ? 2u : 0u) <= 33u && max_len < (1ull << 29) /* a run's count has 29 bits */ && !env_int("TA_TRACE_NO_BITS") && !env_int("TA_NO_BITS")) {
             // The kernel indexes its run lists with 32 bits (pair slot x runs_cap) and its scratch -- checkpoints, run lists, run counts -- is
             // proportional to the pairs of a launch: a batch beyond either bound is worked through in chunks of whole wavefronts, each an
             // ordinary sub-batch on the same stream (65M pairs at k = 32 wrapped the index; a huge batch asked for all of its
@@ -1288,7 +1289,7 @@ static int trace_batch_impl(const ta_strings *a, const ta_strings *b, size_t n, 
             const uint64_t tiles16 = (max_len + 15) / 16 + 1;
             const uint64_t per_pair = tiles16 * lev_bits_trace_ckpt_words(trans) * 4ull + (uint64_t)runs_cap * 4ull + 4ull + 8ull;
             uint64_t chunk = 0xFFFFFFF0ull / (packed_dev ? (cap > runs_cap ? (uint64_t)cap : runs_cap) : (runs_cap ? runs_cap : 1u));
-            const uint64_t held = tls_scratch(9).cap + tls_scratch(8).cap + tls_scratch(7).cap;
+            const uint64_t held = tls_scratch(SLOT_TRACE).cap + tls_scratch(SLOT_AUX_B).cap + tls_scratch(SLOT_AUX_A).cap;
             if (per_pair * n > held && !stream_is_capturing(st)) {   // the scratch has to grow: not beyond half of what is free right now
                 size_t free_b = 0, total_b = 0;
                 if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
@@ -1319,7 +1320,7 @@ static int trace_batch_impl(const ta_strings *a, const ta_strings *b, size_t n, 
         chunk &= ~63ull;
         if (chunk < 64) chunk = 64;
         if (chunk > n) chunk = n;
-        Scratch &es = tls_scratch(12);
+        Scratch &es = tls_scratch(SLOT_SELECT);
         if ((rc = es.ensure((size_t)(chunk * cap_in * sizeof(ta_edit))))) return rc;
         for (uint64_t lo = 0; lo < n; lo += chunk) {
             const size_t cnt = (size_t)((n - lo) < chunk ? (n - lo) : chunk);
@@ -1349,16 +1350,16 @@ static int trace_batch_impl(const ta_strings *a, const ta_strings *b, size_t n, 
     uint64_t waves_per_chunk = ((4ull << 30) / 4) / wave_words;
     if (waves_per_chunk == 0) waves_per_chunk = 1;
     if (waves_per_chunk > waves_all) waves_per_chunk = waves_all;
-    if (wave_words * waves_per_chunk * 4 > tls_scratch(6).cap) {      // the scratch has to grow: not beyond a quarter of what is free right now
+    if (wave_words * waves_per_chunk * 4 > tls_scratch(SLOT_LINES).cap) {      // the scratch has to grow: not beyond a quarter of what is free right now
         size_t free_b = 0, total_b = 0;                                // (asked only then: a captured call must not query the device)
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const uint64_t budget = ((uint64_t)free_b + tls_scratch(6).cap) / 4;
+            const uint64_t budget = ((uint64_t)free_b + tls_scratch(SLOT_LINES).cap) / 4;
             if (wave_words * waves_per_chunk * 4 > budget) waves_per_chunk = (budget / 4) / wave_words;
             if (waves_per_chunk == 0) waves_per_chunk = 1;
         }
     }
     if (wave_words * waves_per_chunk * 4 > (48ull << 30)) { set_last_error_msg("batch traceback: more than 48 GB of records for one wavefront"); return TA_ERR_UNSUPPORTED; }
-    Scratch &ts = tls_scratch(6), &ps = tls_scratch(9);
+    Scratch &ts = tls_scratch(SLOT_LINES), &ps = tls_scratch(SLOT_TRACE);
     const uint32_t path_words = (uint32_t)((2 * max_len) / 16 + 2);                  // 2-bit codes of a pair's path, sixteen per word
     if ((rc = ts.ensure((size_t)(wave_words * waves_per_chunk * 4))) || (rc = ps.ensure((size_t)(waves_per_chunk * pl.PW) * path_words * 4))) return rc;
     LevParams P;

@@ -1,4 +1,6 @@
-// ta_internal.h -- host-side plumbing shared by the C-ABI translation units.
+// ta_internal.h -- host-side plumbing shared by the C-ABI translation units: the error / scratch / stream context, the names of the
+// thread-local scratch slots (ScratchSlot), the host rules over ta_edit_costs and ta_strings that every batch entry shares (defined once
+// in ta_api.hip; their pure halves live in lev_plan.h), and the launchers' prototypes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,13 +32,92 @@ void set_last_kernel_name(const char *fmt, ...) __attribute__((format(printf, 1,
 struct Scratch {
     void *dev = nullptr;
     size_t cap = 0;
+    bool bins_clean = false;    // order_pairs' histogram slots: the last pass over this slot ran to its end (the histogram is zero)
     int ensure(size_t bytes);   // TA_OK / TA_ERR_HIP
     void release();
     ~Scratch();
 };
-constexpr int TA_SCRATCH_SLOTS = 31;   // 18..22: the token entries (ta_tokens.hip); 23..29: the search batch (ta_search_batch.hip); 30: ta_cross.hip
-constexpr int TA_SLOT_SEARCH_HAY = 17;        // the host search entries' haystack staging: nothing else writes it (ta_levenshtein_search_resume relies on that)
-Scratch &tls_scratch(int which);
+// The thread-local scratch slots.  Everything a call enqueues goes to ONE stream, and a later call of the thread on another stream first
+// waits for the earlier one (StreamGuard): two users of a slot that enqueue one after the other never meet.  A slot may therefore be shared
+// by entry points that never call each other, and inside one call by buffers of which the first is dead (its last kernel enqueued, or its
+// value read back under a synchronisation) before the second is ensured.  What must NOT share a slot: two buffers live in the same call,
+// and anything that keeps its CONTENT from one call to the next (marked "persists").  The numbers are baked into captured graphs through
+// the buffers' addresses and are part of nothing else.
+enum ScratchSlot {
+    SLOT_PAIR_STAGE = 0,     // stage_pair (ta_api.hip): a single call's long pair and its result word, live until the call's fetch.  Alone.
+    SLOT_SEARCH_HITS = 1,    // ta_search.hip: the host search entries' hit buffer (run_search_host, first_hit_windows).  Alone.
+    SLOT_SEARCH_CTL = 2,     // ta_search.hip: the SearchCtl / counters of one search pass; best_hits_of reuses its first words once the pass's
+                             // count has been read back.  Search entries only.
+    SLOT_COUNT = 3,          // ta_api.hip: side_max_len's word (read back under a synchronisation before anything else is enqueued), then the
+                             // list counters of the same call: the unit prefilter's, the exp loop's (two per round).
+    SLOT_SUBSET_A = 4,       // the exp loop's ping-pong subset lists (4 and 5) / the unit prefilter's survivor list (4): ta_levenshtein_exp_batch
+    SLOT_SUBSET_B = 5,       // and ta_levenshtein_k_batch never call each other.  5 is also the search filter's list of flagged blocks (ta_search.hip,
+                             // search_dev_core): no search entry runs a distance pass.
+    SLOT_LINES = 6,          // what ONE kernel of a pass needs beside its inputs: the stripe boundary lines of lev_wide.hip / lev_widebits.hip (every
+                             // launcher there; lev_pass runs one of them per pass, the exp loop's passes follow each other on the stream), those of
+                             // trace_widebits, the memory-backed columns of ta_search.hip (needles beyond 32 bytes) and the DP band kernel's
+                             // traceback records (ta_levenshtein_trace, the record route of ta_levenshtein_trace_batch: neither runs a lev_wide /
+                             // lev_widebits launcher; the token entries' wide pass follows the byte pass on the stream).
+    SLOT_AUX_A = 7,          // ta_search.hip: the needle's device copy (needles beyond 32 / 64 bytes) | trace_bits_batch: the run counts.
+    SLOT_AUX_B = 8,          // lev_widebits.hip: the tiled form's stripe states (4 and 5 hold the exp loop's subsets while it runs) | trace_bits_batch:
+                             // the run lists -- ensured after its distance pass (lev_pass, which may take the tiled form) has been enqueued.
+    SLOT_TRACE = 9,          // traceback records of one pair (trace_widebits, trace_wide, ta_tokens.hip: wide_pair_u32) | trace_bits_batch: the
+                             // checkpoints | the record route of ta_levenshtein_trace_batch: the walked paths.  One route per call; the packed form's
+                             // sub-batches are calls of their own, one after the other.
+    SLOT_EXP_BOUND = 10,     // ta_levenshtein_exp_batch: the bag lower bounds ...
+    SLOT_EXP_WORK = 11,      // ... and the list of pairs a bounded round takes.  Alone.
+    SLOT_SELECT = 12,        // ta_search.hip: a Best pass's SearchSlots, then (after the pass's synchronisation) best_hits_of's selection |
+                             // ta_levenshtein_trace_batch_packed: the ta_edit records of a sub-batch, live across the inner record-route call
+                             // (which uses 6 and 9).
+    SLOT_ORDER = 13,         // order_pairs for the distance entries (ta_levenshtein_k_batch, _exp_batch, trace_bits_batch): the length-ordered list,
+    SLOT_ORDER_BINS = 14,    // read until the call's last pass, and its histogram -- persists (zero between complete passes; Scratch::bins_clean).
+    SLOT_ALPHA_BAD = 15,     // ta_levenshtein_k_batch_alphabet: the pairs with a byte outside the alphabet ...
+    SLOT_ALPHA_COUNT = 16,   // ... and the two counters taken in turn -- persists.  Alone.
+    SLOT_SEARCH_HAY = 17,    // ta_search.hip: the host search entries' haystack staging -- persists (ta_levenshtein_search_resume); nothing else writes it.
+    SLOT_TOK_CA = 18,        // ta_tokens.hip: the byte codes of both sides, live across the byte entry point the token entry calls,
+    SLOT_TOK_CB = 19,
+    SLOT_TOK_TABLE = 20,     // the compaction's hash tables,
+    SLOT_TOK_OVF = 21,       // tok_side's word (read back under a synchronisation), then the overflow count and list, live until the overflow pass,
+    SLOT_TOK_STAGE = 22,     // one host pair of u32 items and its result word (wide_pair_u32).  18..22: the token entries alone.
+    SLOT_SB_ORDER = 23,      // ta_search_batch.hip: order_pairs for both search-batch entries -- its own list and histogram (24 persists like 14), so a
+    SLOT_SB_BINS = 24,       // search batch and a distance batch enqueued back to back never share an order.
+    SLOT_SB_CTL = 25,        // word 0: Route S's candidate count; words 4..7 (two 64-bit words at offset 2): measure_max_lens.
+    SLOT_SB_LIST = 26,       // Route S: the candidate pairs ...
+    SLOT_SB_SPAN = 27,       // ... and their spans.
+    SLOT_SB_COL = 28,        // the memory-backed columns (needles beyond 32 bytes).  23..28: the search batch alone.
+    SLOT_CROSS_CTL = 30,     // ta_cross.hip: measure_max_lens' two 64-bit words.  Alone.
+    TA_SCRATCH_SLOTS
+};
+Scratch &tls_scratch(ScratchSlot which);
+
+// ---- host rules over the C structs, stated once (the pure halves: lev_plan.h)
+static inline bool costs_ok(const ta_edit_costs *c) {       // EditCosts::new, src/levenshtein.rs:44-52
+    return c && lev_costs_valid(c->mismatch_cost, c->gap_cost, c->has_transpose != 0, c->transpose_cost);
+}
+static inline bool costs_unit(const ta_edit_costs *c) {     // LEVENSHTEIN_COSTS / RDAMERAU_COSTS
+    return lev_is_unit(c->mismatch_cost, c->gap_cost, c->start_gap_cost, c->has_transpose != 0, c->transpose_cost);
+}
+static inline uint32_t costs_scale(const ta_edit_costs *c) {   // 1: unit family, g: g times one, 0: neither (lev_cost_scale)
+    return lev_cost_scale(c->mismatch_cost, c->gap_cost, c->start_gap_cost, c->has_transpose != 0, c->transpose_cost);
+}
+static inline StrView view_of(const ta_strings *s) { return StrView{s->blob, s->off, s->stride, s->len}; }
+// the length bound of a batch side: known without measuring (strided, or CSR with max_len given), and its value
+static inline bool side_bound_known(const ta_strings *s) { return !s->off || s->max_len; }
+static inline uint64_t side_bound(const ta_strings *s) { return s->off ? s->max_len : s->len; }
+// the longest string of two sides of na / nb strings: side_bound where it is known, else measured on the device into dst[0] (a) and dst[1]
+// (b) -- the caller's two 64-bit words of scratch -- with one copy and one synchronisation for both; no launch for a known side
+int measure_max_lens(const ta_strings *a, uint32_t na, const ta_strings *b, uint32_t nb, unsigned long long *dst, hipStream_t st,
+                     uint64_t *ma, uint64_t *mb);
+// The pairs of a ragged batch in length order (util_kernels.hip: length_order_launch) into the caller's slots; *order_out = the list.
+// The histogram must be zero on entry and every complete pass leaves it zero: Scratch::bins_clean of `bins_slot` says this thread's last
+// pass over it was complete -- after one that failed midway the histogram is zeroed again (by the graph-safe fill kernel) instead of trusted.
+int order_pairs(const ta_strings *a, const ta_strings *b, uint32_t n, uint32_t u, uint64_t max_len, bool by_steps, bool exact,
+                ScratchSlot order_slot, ScratchSlot bins_slot, hipStream_t st, const uint32_t **order_out, bool *exact_columns);
+// the pointer and size checks every pair-batch entry starts with (bytes: `what` = "null blob", tokens: "null data")
+int check_batch_args(const void *a, const void *b, const void *a_data, const void *b_data, size_t n, const void *out, const char *what);
+static inline int check_batch_args(const ta_strings *a, const ta_strings *b, size_t n, const void *out) {
+    return check_batch_args(a, b, a ? a->blob : nullptr, b ? b->blob : nullptr, n, out, "null blob");
+}
 
 // Per-thread context of the single-call host API: its own non-blocking stream (concurrent callers never meet on the null
 // stream) and a pinned, device-mapped staging buffer -- a short pair is memcpy'd there, the kernel reads it in place and
@@ -237,7 +318,7 @@ hipError_t ham_search_batch_launch(const HamBatchParams &P, bool bits, hipStream
 struct CrossParams {
     StrView q, t;                 // queries (every one at most 32 nw bytes), targets
     uint32_t nq, nt;
-    uint32_t k, g;                // the unit threshold; distances are reported times g (lev_unit_scale, 1 for the unit families)
+    uint32_t k, g;                // the unit threshold; distances are reported times g (lev_cost_scale)
     uint32_t qtile;               // queries per wavefront: ceil(nq / qtile) <= 65535
     ta_cross_hit *hits;           // device: cap records, or nullptr with cap = 0
     uint64_t cap;

@@ -414,7 +414,7 @@ static int pairs_host(PairOp op, const ta_strings *a, const ta_strings *b, size_
                       uint32_t *packed = nullptr, uint32_t *n_edits = nullptr, size_t cap = 0) {
     if (!host_strings_ok(a, n) || !host_strings_ok(b, n) || (!out && n) || n > 0xFFFFFFF0ull) { set_last_error_msg("bad batch arguments"); return TA_ERR_ARG; }
     if (op == OP_TRACE && n && (!packed || !n_edits || cap == 0 || cap > 0xFFFFFFFFull)) { set_last_error_msg("bad batch arguments"); return TA_ERR_ARG; }
-    if (op != OP_HAMMING && (!costs || ta_edit_costs_new(costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose, costs->transpose_cost, nullptr) != TA_OK))
+    if (op != OP_HAMMING && !costs_ok(costs))
         return TA_ERR_BAD_COSTS;
     if (!device_ready()) return TA_ERR_HIP;
     if (n == 0) return TA_OK;
@@ -741,7 +741,7 @@ int ta_sharded_pairs_upload(const ta_strings *a, const ta_strings *b, size_t n, 
 
 static int sharded_pairs_run(ta_sharded_pairs *S, PairOp op, uint32_t k, const ta_edit_costs *costs, uint32_t *out, int download_results) {
     if (!S || (!out && download_results && S->n)) return TA_ERR_ARG;
-    if (op != OP_HAMMING && (!costs || ta_edit_costs_new(costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose, costs->transpose_cost, nullptr) != TA_OK))
+    if (op != OP_HAMMING && !costs_ok(costs))
         return TA_ERR_BAD_COSTS;
     const ta_edit_costs c = costs ? *costs : ta_edit_costs{1, 1, 0, 0, 0};
     return run_on(*S->pool, S->shards.size(), [&](size_t r, Worker &w) -> int {
@@ -843,7 +843,7 @@ int ta_sharded_haystack_levenshtein_search(ta_sharded_haystack *H, const uint8_t
                                            const ta_edit_costs *costs, ta_match **out, size_t *n_out) {
     if (!H || !out || !n_out || (!needle && needle_len)) return TA_ERR_ARG;
     *out = nullptr; *n_out = 0;
-    if (!costs || ta_edit_costs_new(costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose, costs->transpose_cost, nullptr) != TA_OK)
+    if (!costs_ok(costs))
         return TA_ERR_BAD_COSTS;
     if (needle_len == 0) return TA_OK;                                          // unanchored: src/levenshtein.rs:1641-1643
     if (ta_edit_costs_check_search(costs) != TA_OK) return TA_ERR_BAD_COSTS;     // :1965

@@ -1,5 +1,5 @@
 // ta_search.hip -- search entry points of the C ABI: special cases, haystack tiling, hit gathering,
-// and the order-dependent Best post-pass (host).
+// and the order-dependent Best post-pass (host).  The cost rules (costs_ok, costs_unit) and the scratch slots' names: ta_internal.h.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -14,16 +14,6 @@
 
 namespace ta {
 hipError_t has_zero_byte_launch(const uint8_t *p, uint64_t len, uint32_t *flag, hipStream_t s);
-
-static bool search_costs_ok(const ta_edit_costs *c) {
-    if (!c || !(c->mismatch_cost > 0) || !(c->gap_cost > 0)) return false;
-    if (c->has_transpose) {
-        if (!(c->transpose_cost > 0) || !((c->transpose_cost >> 1) < c->mismatch_cost) ||
-            !((c->transpose_cost >> 1) < c->gap_cost))
-            return false;
-    }
-    return true;
-}
 
 // tile size: enough tiles to fill the chip (>= ~128K lanes) while keeping the halo overhead small
 static uint32_t pick_tile(uint64_t hay_len, uint32_t halo) {
@@ -61,7 +51,7 @@ static int best_hits_of(const ta_match *hits_dev, uint64_t count, std::vector<ta
     v.clear();
     if (count == 0) return TA_OK;
     const uint32_t cap = 1u << 16;                                // best hits kept on the first try (rarely more than a handful)
-    Scratch &sel = tls_scratch(12), &cnt = tls_scratch(2);
+    Scratch &sel = tls_scratch(SLOT_SELECT), &cnt = tls_scratch(SLOT_SEARCH_CTL);
     int rc;
     if ((rc = sel.ensure((size_t)cap * sizeof(ta_match))) || (rc = cnt.ensure(64))) return rc;
     uint32_t *ctr = (uint32_t *)cnt.dev;                          // [0] count, [1] min k
@@ -99,13 +89,13 @@ static void sort_by_end(std::vector<ta_match> &v) {
 static int search_dev_core(const uint8_t *needle_host, size_t needle_len, const uint8_t *haystack_dev, size_t haystack_len,
                            uint32_t k, const ta_edit_costs *costs, int anchored, uint64_t base, uint64_t emit_from,
                            ta_match *hits_dev, size_t cap, uint64_t *count_host, std::vector<ta_match> *best, hipStream_t st) {
-    if (!search_costs_ok(costs)) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;
     if (ta_edit_costs_check_search(costs) != TA_OK) return TA_ERR_BAD_COSTS;         // :1965
     if (needle_len == 0) { set_last_error_msg("empty needle is handled by the host entry point"); return TA_ERR_ARG; }
     if (needle_len > 0xFFFFu) { set_last_error_msg("needle longer than 65535 bytes"); return TA_ERR_ARG; }
     if (!device_ready()) return TA_ERR_HIP;
     StreamGuard guard(st);
-    Scratch &cnt = tls_scratch(2);
+    Scratch &cnt = tls_scratch(SLOT_SEARCH_CTL);
     int rc = cnt.ensure(sizeof(SearchCtl) + 64);
     if (rc) return rc;
     SearchParams P;
@@ -124,13 +114,13 @@ static int search_dev_core(const uint8_t *needle_host, size_t needle_len, const 
     if (anchored) P.halo = 0;
     if (needle_len > 32) {
         // memory-backed column: needle on the device, 6 arrays of (n+1) u32 per tile; keep the scratch <= ~256 MB
-        Scratch &nd = tls_scratch(7);
+        Scratch &nd = tls_scratch(SLOT_AUX_A);
         if ((rc = nd.ensure(needle_len + 16))) return rc;
         TA_HIP(hipMemcpyAsync(nd.dev, needle_host, needle_len, hipMemcpyHostToDevice, st));
         P.needle_dev = (const uint8_t *)nd.dev;
     }
     auto mem_column_scratch = [&]() -> int {           // the lane-per-tile kernel over everything, needle > 32 bytes
-        Scratch &cs = tls_scratch(6);
+        Scratch &cs = tls_scratch(SLOT_LINES);
         const uint64_t per_tile = 6ull * (needle_len + 1) * 4ull;
         uint64_t max_tiles = (256ull << 20) / per_tile;
         if (max_tiles < 64) max_tiles = 64;
@@ -149,8 +139,7 @@ static int search_dev_core(const uint8_t *needle_host, size_t needle_len, const 
     if (anchored)           // every cost must stay below the packed form's "no gap yet" marker (lev_search_body.h)
         packed = needle_len <= 32 && k <= 30000u && h <= 60000u && !env_str("TA_SEARCH_UNPACKED") &&
                  srch_anchored_packed_ok(h, (uint32_t)needle_len, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost);
-    const bool unit = costs->mismatch_cost == 1 && costs->gap_cost == 1 && costs->start_gap_cost == 0 &&
-                      (!costs->has_transpose || costs->transpose_cost == 1);
+    const bool unit = costs_unit(costs);
     const bool trans = costs->has_transpose != 0;
     // The filter scans with unit costs; under any other EditCosts it runs with k' = srch_filter_k (lev_search_body.h): a superset
     // filter -- every alignment of weighted cost <= k has at most k' unit edits -- in front of the exact kernel, which knows the
@@ -161,7 +150,7 @@ static int search_dev_core(const uint8_t *needle_host, size_t needle_len, const 
     bool searched = false;
     unsigned long long c = 0;
     if (filter_ok) {
-        Scratch &ls = tls_scratch(5);
+        Scratch &ls = tls_scratch(SLOT_SUBSET_B);
         uint64_t cap_list = h / FILTER_BLOCK + 2;
         if (cap_list > (4u << 20)) cap_list = 4u << 20;
         if ((rc = ls.ensure((size_t)cap_list * 4))) return rc;
@@ -181,7 +170,7 @@ static int search_dev_core(const uint8_t *needle_host, size_t needle_len, const 
         if (needle_len <= 64 && k <= 30000u) {
             // one wavefront per flagged block; no host round trip: the report arrives with the stream synchronisation
             PinBox &box = search_report_box();
-            Scratch &cd = tls_scratch(12);
+            Scratch &cd = tls_scratch(SLOT_SELECT);
             if ((rc = box.ensure()) || (best && (rc = cd.ensure((size_t)SEARCH_SLOT_CAP * sizeof(SearchSlot))))) return rc;
             TA_HIP(lev_search_wave_launch(P, trans, best != nullptr, (const uint32_t *)ls.dev, (uint32_t)cap_list, ctl, (SearchSlot *)cd.dev,
                                           box.dev, st));
@@ -206,7 +195,7 @@ static int search_dev_core(const uint8_t *needle_host, size_t needle_len, const 
             // dense matches: the exact kernel over everything is cheaper than (64 + halo) columns per flagged block
             if (n_list <= cap_list && (uint64_t)n_list * (FILTER_BLOCK + P.halo) < h / 2) {
                 if (n_list) {                                            // one memory-backed column per flagged block
-                    Scratch &cs = tls_scratch(6);
+                    Scratch &cs = tls_scratch(SLOT_LINES);
                     if ((rc = cs.ensure((size_t)(6ull * (needle_len + 1) * 4ull * n_list)))) return rc;
                     P.col_scratch = (uint32_t *)cs.dev;
                 }
@@ -290,7 +279,7 @@ static int hamming_search_dev_impl(const uint8_t *needle_host, size_t needle_len
     if (in_box) *in_box = false;
     if (needle_len == 0 || needle_len > haystack_len) return TA_OK;                     // src/hamming.rs:455-461
     StreamGuard guard(st);
-    Scratch &cnt = tls_scratch(2);
+    Scratch &cnt = tls_scratch(SLOT_SEARCH_CTL);
     PinBox &box = search_report_box();
     int rc = cnt.ensure(16);
     if (rc || (rc = box.ensure())) return rc;
@@ -302,7 +291,7 @@ static int hamming_search_dev_impl(const uint8_t *needle_host, size_t needle_len
     // (the round-1 SWAR kernel -- needles beyond 64 bytes the phased filter does not take, or TA_HAMMING_SEARCH_SWAR=1 -- reads the device copy)
     P.needle_dev = nullptr;
     if (needle_len > 64 || env_str("TA_HAMMING_SEARCH_SWAR") || (needle_len > 32 && tuning_enabled())) {   // (any A/B switch may route to the kernel that reads the device copy)
-        Scratch &nd = tls_scratch(7);
+        Scratch &nd = tls_scratch(SLOT_AUX_A);
         if ((rc = nd.ensure(needle_len + 16))) return rc;
         TA_HIP(hipMemcpyAsync(nd.dev, needle_host, needle_len, hipMemcpyHostToDevice, st));
         P.needle_dev = (const uint8_t *)nd.dev;
@@ -420,7 +409,7 @@ static int give(std::vector<ta_match> &v, ta_match **out, size_t *n_out) {
 // stage a haystack into device scratch (with read slack) and collect the All-mode hits, sorted by end; everything runs on
 // the calling thread's own stream.  The hit buffer starts at min(haystack_len + 2, 4M) records; a denser result (All mode
 // over a big haystack, k >= needle_len) reports its true count, and the pass is repeated once with room for exactly that.
-// What ta_levenshtein_search_first left in this thread's haystack staging buffer (tls_scratch(TA_SLOT_SEARCH_HAY)): the first `upto` bytes of the caller's
+// What ta_levenshtein_search_first left in this thread's haystack staging buffer (tls_scratch(SLOT_SEARCH_HAY)): the first `upto` bytes of the caller's
 // haystack.  ta_levenshtein_search_resume -- "the rest of the All-mode result over THE SAME haystack" -- uploads only what is missing.
 struct ResidentHay { const uint8_t *host = nullptr; size_t len = 0; uint64_t upto = 0; const void *dev = nullptr; uint8_t fp[128] = {}; };
 // a content fingerprint of the uploaded prefix (its first and last 64 bytes): a caller that reuses the pointer for other bytes -- the C header
@@ -455,14 +444,12 @@ static int run_search_host(const uint8_t *haystack, size_t haystack_len, std::ve
         if (rc == TA_OK) {
             const ta_match *h = (const ta_match *)(cx.pin + hay_pad);
             hits.assign(h, h + count);
-            std::sort(hits.begin(), hits.end(), [](const ta_match &x, const ta_match &y) {
-                return x.end != y.end ? x.end < y.end : x.start < y.start;
-            });
+            sort_by_end(hits);
             return TA_OK;
         }
         if (rc != TA_ERR_CAPACITY) return rc;
     }
-    Scratch &hs = tls_scratch(TA_SLOT_SEARCH_HAY), &ob = tls_scratch(1);
+    Scratch &hs = tls_scratch(SLOT_SEARCH_HAY), &ob = tls_scratch(SLOT_SEARCH_HITS);
     if (hs.cap < haystack_len + TA_BLOB_SLACK + 64) resident_upto = 0;                          // (the buffer is about to be re-allocated)
     if ((rc = hs.ensure(haystack_len + TA_BLOB_SLACK + 64))) return rc;
     size_t cap = haystack_len + 2;
@@ -486,9 +473,7 @@ static int run_search_host(const uint8_t *haystack, size_t haystack_len, std::ve
         TA_HIP(hipMemcpyAsync(hits.data(), ob.dev, count * sizeof(ta_match), hipMemcpyDeviceToHost, cx.st));
         TA_HIP(hipStreamSynchronize(cx.st));
     }
-    std::sort(hits.begin(), hits.end(), [](const ta_match &x, const ta_match &y) {
-        return x.end != y.end ? x.end < y.end : x.start < y.start;
-    });
+    sort_by_end(hits);
     return TA_OK;
 }
 
@@ -500,7 +485,7 @@ int ta_levenshtein_search_simd_with_opts(const uint8_t *needle, size_t needle_le
                                          ta_match **out, size_t *n_out) {
     if (!out || !n_out || (!needle && needle_len) || (!haystack && haystack_len)) return TA_ERR_ARG;
     *out = nullptr; *n_out = 0;
-    if (!search_costs_ok(costs)) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;
     std::vector<ta_match> res;
     if (needle_len == 0) {                                                 // src/levenshtein.rs:1919-1963
         if (!anchored) return TA_OK;
@@ -547,7 +532,7 @@ static int first_hit_windows(const uint8_t *needle, size_t needle_len, const uin
     *found = 0;
     const uint32_t unit_k = lev_sat_sub(k, costs->start_gap_cost) / costs->gap_cost;
     const uint64_t halo = (uint64_t)needle_len + unit_k + 2;
-    Scratch &ob = tls_scratch(1);
+    Scratch &ob = tls_scratch(SLOT_SEARCH_HITS);
     const size_t cap = 1u << 16;                                  // hits kept per window; a denser window is cut down (below)
     int rc = ob.ensure(cap * sizeof(ta_match));
     if (rc) return rc;
@@ -591,7 +576,7 @@ int ta_levenshtein_search_first_dev(const uint8_t *needle_host, size_t needle_le
                                     ta_match *out, int *found, void *stream) {
     if (!out || !found || (!needle_host && needle_len) || (!haystack_dev && haystack_len)) return TA_ERR_ARG;
     *found = 0;
-    if (!search_costs_ok(costs) || ta_edit_costs_check_search(costs) != TA_OK) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs) || ta_edit_costs_check_search(costs) != TA_OK) return TA_ERR_BAD_COSTS;
     if (needle_len == 0 || haystack_len == 0) return TA_OK;
     return first_hit_windows(needle_host, needle_len, haystack_dev, haystack_len, k, costs, base, out, found, (hipStream_t)stream,
                              [](uint64_t, uint64_t) { return (int)TA_OK; });
@@ -602,7 +587,7 @@ int ta_levenshtein_search_first(const uint8_t *needle, size_t needle_len, const 
     if (!out || !found || (!needle && needle_len) || (!haystack && haystack_len)) return TA_ERR_ARG;
     *found = 0;
     resident_hay() = ResidentHay{};                                            // (set again below if this call uploads a prefix)
-    if (!search_costs_ok(costs)) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;
     if (needle_len == 0) {                                                      // src/levenshtein.rs:1919-1963
         if (anchored) { *out = ta_match{0, 0, 0, 0}; *found = 1; }
         return TA_OK;
@@ -626,7 +611,7 @@ int ta_levenshtein_search_first(const uint8_t *needle, size_t needle_len, const 
     CallCtx &cx = call_ctx();
     int rc = cx.ensure();
     if (rc) return rc;
-    Scratch &hs = tls_scratch(TA_SLOT_SEARCH_HAY);
+    Scratch &hs = tls_scratch(SLOT_SEARCH_HAY);
     if ((rc = hs.ensure(haystack_len + TA_BLOB_SLACK + 64))) return rc;
     uint8_t *hd = (uint8_t *)hs.dev;
     hipStream_t st = cx.st;

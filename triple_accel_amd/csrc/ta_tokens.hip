@@ -3,6 +3,7 @@
 // A batch of u32 sequences is compacted pair by pair into byte codes (sym_compact_body.h) that keep the cross-sequence equality
 // relation, the byte entry point runs on the codes, and the pairs the compaction could not code (overflow list, its length on the
 // device) are answered by the DP wide kernel over 32-bit items (lev_wide.hip), on the same stream after the byte pass.
+// The cost check, the batch argument check and the scratch slots' names (SLOT_TOK_*) are the shared ones of ta_internal.h.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,19 +16,10 @@
 
 namespace ta {
 
-static constexpr int SLOT_CA = 18, SLOT_CB = 19, SLOT_TABLE = 20, SLOT_OVF = 21, SLOT_STAGE = 22;
-
-static bool tok_costs_ok(const ta_edit_costs *c) {   // EditCosts::new, src/levenshtein.rs:44-52 (as ta_api.hip)
-    ta_edit_costs t;
-    return c && ta_edit_costs_new(c->mismatch_cost, c->gap_cost, c->start_gap_cost, c->has_transpose, c->transpose_cost, &t) == TA_OK;
-}
-
 static StrView tok_view(const ta_tokens *t) { return StrView{(const uint8_t *)t->data, t->off, t->stride, t->len}; }
 
 static int tok_check(const ta_tokens *a, const ta_tokens *b, size_t n, const void *out) {
-    if (!a || !b || (!out && n) || n > 0xFFFFFFF0ull) { set_last_error_msg("bad batch arguments"); return TA_ERR_ARG; }
-    if (n && (!a->data || !b->data)) { set_last_error_msg("null data"); return TA_ERR_ARG; }
-    return TA_OK;
+    return check_batch_args(a, b, a ? a->data : nullptr, b ? b->data : nullptr, n, out, "null data");
 }
 
 // longest sequence of a side (given, implied or measured: one synchronisation) and the items `data` holds (CSR: off[n])
@@ -36,7 +28,7 @@ static int tok_side(const ta_tokens *t, uint32_t n, hipStream_t st, uint64_t *ma
     *max_len = t->max_len;
     *items = t->len;
     if (t->max_len && t->len) return TA_OK;
-    Scratch &sc = tls_scratch(SLOT_OVF);
+    Scratch &sc = tls_scratch(SLOT_TOK_OVF);
     int rc = sc.ensure(64);
     if (rc) return rc;
     uint32_t *d = (uint32_t *)sc.dev;
@@ -80,7 +72,7 @@ static int tok_compact(const ta_tokens *a, const ta_tokens *b, uint32_t n, hipSt
         waves &= ~3u;
         if (!waves) waves = 4;
     }
-    Scratch &sa = tls_scratch(SLOT_CA), &sb = tls_scratch(SLOT_CB), &tb = tls_scratch(SLOT_TABLE), &ov = tls_scratch(SLOT_OVF);
+    Scratch &sa = tls_scratch(SLOT_TOK_CA), &sb = tls_scratch(SLOT_TOK_CB), &tb = tls_scratch(SLOT_TOK_TABLE), &ov = tls_scratch(SLOT_TOK_OVF);
     if ((rc = sa.ensure(ia + TA_BLOB_SLACK)) || (rc = sb.ensure(ib + TA_BLOB_SLACK)) || (rc = ov.ensure(64 + (size_t)n * 4))) return rc;
     if (table_cap && (rc = tb.ensure((size_t)((waves + 3u) & ~3u) * table_cap * 12u))) return rc;
     SymCompactParams P;
@@ -135,7 +127,7 @@ static int wide_pair_u32(const uint32_t *a, size_t la, const uint32_t *b, size_t
     if (n > 0xFFFFFFF0ull || m > 0xFFFFFF00ull) { set_last_error_msg("token sequence too long"); return TA_ERR_ARG; }
     const uint64_t tcols = (uint64_t)m + 64, code_words = res ? ((n + 2047) / 2048) * tcols * 64ull * 2ull : 0;
     if (code_words * 4ull > (8ull << 30)) { set_last_error_msg("traceback: more than 8 GB of traceback records"); return TA_ERR_UNSUPPORTED; }
-    Scratch &stg = tls_scratch(SLOT_STAGE), &ts = tls_scratch(9);
+    Scratch &stg = tls_scratch(SLOT_TOK_STAGE), &ts = tls_scratch(SLOT_TRACE);
     int rc;
     if ((rc = stg.ensure((n + m + 4) * 4))) return rc;
     if (res && (rc = ts.ensure((size_t)code_words * 4 + 4))) return rc;
@@ -216,7 +208,7 @@ int ta_levenshtein_k_batch_tokens(const ta_tokens *a, const ta_tokens *b, size_t
                                   const ta_edit_costs *costs, uint32_t *out_dev, void *stream) {
     int rc = tok_check(a, b, n, out_dev);
     if (rc) return rc;
-    if (!tok_costs_ok(costs)) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;
     if (!device_ready()) return TA_ERR_HIP;
     if (n == 0) return TA_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -231,7 +223,7 @@ int ta_levenshtein_exp_batch_tokens(const ta_tokens *a, const ta_tokens *b, size
                                     const ta_edit_costs *costs, uint32_t *out_dev, void *stream) {
     int rc = tok_check(a, b, n, out_dev);
     if (rc) return rc;
-    if (!tok_costs_ok(costs)) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;
     if (!device_ready()) return TA_ERR_HIP;
     if (n == 0) return TA_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -247,7 +239,7 @@ int ta_levenshtein_trace_batch_tokens(const ta_tokens *a, const ta_tokens *b, si
     int rc = tok_check(a, b, n, out_dev);
     if (rc) return rc;
     if (n && (!edits_dev || !n_edits_dev)) { set_last_error_msg("bad batch arguments"); return TA_ERR_ARG; }
-    if (!tok_costs_ok(costs)) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;
     if (!device_ready()) return TA_ERR_HIP;
     if (n == 0) return TA_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -294,7 +286,7 @@ int ta_levenshtein_tokens(const uint32_t *a, size_t a_len, const uint32_t *b, si
                           const ta_edit_costs *costs, uint32_t *out, ta_edit **edits, size_t *n_edits) {
     if (!out || (!a && a_len) || (!b && b_len) || (edits && !n_edits)) return TA_ERR_ARG;
     if (edits) { *edits = nullptr; *n_edits = 0; }
-    if (!tok_costs_ok(costs)) return TA_ERR_BAD_COSTS;
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;
     if (!device_ready()) return TA_ERR_HIP;
     std::vector<uint8_t> ca, cb;
     if (host_codes(a, a_len, b, b_len, ca, cb)) {
