@@ -35,6 +35,7 @@ HALF = 4.2
 # (config, translation unit, mangled-name regex of the dominant kernel, columns / steps one iteration of the block advances)
 KERNELS = [
     ("cfg2", "lev_bits.hip", r"_ZN2ta18lev_bits_s8_kernelILb0ELb1ELb0E\w*", "8 columns of 64 pairs (33-diagonal band, stride-8 window, line form)", "all_live"),
+    ("cfg2_tab", "lev_bits_tab.hip", r"_ZN2ta19lev_bits_tab_kernel\w*", "32 columns of 64 pairs: the two whole 16-column spans (33-diagonal band, match vector from nibble tables in LDS)", "tab_spans"),
     ("cfg4", "lev_bits.hip", r"_ZN2ta16lev_bits2_kernelILb1ELb0E\w*", "the span loop: 16 columns of 128 pairs with their commits (11-diagonal band + transposition, two pairs per lane, stride-8 window)"),
     ("cfg2w", "lev_band_score.hip", r"_ZN2ta21lev_band_score_kernelILi12ELb1ELi0ELb1E\w*", "four iterations = eight anti-diagonals = four columns of 64 pairs x 12 diagonals (affine gaps, score form)"),
     ("cfg4w", "lev_band_score.hip", r"_ZN2ta21lev_band_score_kernelILi6ELb1ELi1ELb1E\w*", "four iterations = eight anti-diagonals = four columns of 64 pairs x 6 diagonals (affine gaps, transposition)"),
@@ -127,6 +128,12 @@ def hot_loop(body, pick="largest"):
         def selects(g):
             return sum(1 for _, ins, _ in g for x in ins if x.startswith("v_cndmask"))
         hdr = min((h for h in groups if valu(groups[h]) >= 0.8 * top), key=lambda h: selects(groups[h]))
+    if pick == "tab_spans":
+        # lev_bits_tab_kernel: straight-line spans of 16 columns, one per phase of the 32-slot ring, inside the block loop -- the two
+        # basic blocks with 64 table flips each (the warm-up spans hold 32, the cut-short spans are split by their guards)
+        spans = [(lab, ins, text) for lab, ins, _, text in bl if sum(1 for x in ins if x.startswith("ds_xor")) == 64]
+        assert len(spans) == 2, [lab for lab, _, _ in spans]
+        return "+".join(lab for lab, _, _ in spans), [x for _, ins, _ in spans for x in ins], [], "\n".join("%s:%s" % (lab, text) for lab, _, text in spans)
     if pick == "smallest_hot":
         # the kernel holds several copies of its inner loop (chunk form, line form specialised by the answer's word): the BASELINE
         # configuration runs the specialised line-form copy -- the leanest of the hot loops

@@ -147,6 +147,8 @@ hipError_t lev_bits_launch(const LevParams &P0, const LevBitsPlan &pl, bool tran
     if (early_out_enabled()) P.tune |= 2u;
     const bool line_form = !P.a.off && !P.b.off && !(P.tune & 1u);
     if (pl.s8 && line_form) P.lds_per_wave = 64u * (52u + 36u);       // the stride-8 line form's small rings (lev_bits_body.h)
+    // big launches of the stride-8 line form's Levenshtein case: the table form (lev_bits_tab_body.h)
+    if (tab_form_wanted(P, pl, trans, line_form, line_form && pl.s8 && (P.tune & 2u) != 0u, max_len)) return lev_bits_tab_launch(P, s, grid_out, lds_out);
     const uint32_t waves = (P.n + 63u) / 64u;
     // 4 waves per block while four rings fit a quarter of the CU's LDS; else one wave per block so that the CU packs
     // as many waves as the LDS holds.  TA_BITS_WPB pins the waves per block, TA_BITS_BLOCK_LDS the block's LDS request

@@ -1,0 +1,33 @@
+// lev_bits_tab.hip -- gfx950 instantiation of the table form of the bit-parallel band kernel (lev_bits_tab_body.h).
+#include <hip/hip_runtime.h>
+
+#include "lev_bits_tab_body.h"
+#include "lev_plan.h"
+#include "wave_tab.h"
+#include "ta_internal.h"
+
+namespace ta {
+
+// One wavefront per block: the nibble tables sit at the start of the block's LDS, address 0 (the body's table addresses are absolute:
+// lane * 4 | nibble << 8 as they stand), and the CU packs as many blocks as its LDS holds -- 11 of 13,824 bytes, three on three of its
+// four SIMDs: the registers are capped for three wavefronts per SIMD.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void lev_bits_tab_kernel(LevParams P) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    if (DevTab::lds_address(lds, lds) != 0u) return;         // (never: this kernel has no static LDS in front of the dynamic one)
+    LevBitsTab<DevWave, DevTab>::run(P, blockIdx.x, lds);
+}
+
+hipError_t lev_bits_tab_launch(const LevParams &P0, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out) {
+    LevParams P = P0;
+    P.lds_per_wave = LEV_TAB_LDS_PER_WAVE;
+    const uint32_t waves = (P.n + 63u) / 64u;
+    const uint32_t grid = waves;
+    if (grid_out) *grid_out = grid;
+    if (lds_out) *lds_out = LEV_TAB_LDS_PER_WAVE;
+    set_last_kernel_name("lev_bits_tab_kernel");
+    if (grid == 0) return hipSuccess;
+    hipLaunchKernelGGL(lev_bits_tab_kernel, dim3(grid), dim3(64), LEV_TAB_LDS_PER_WAVE, s, P);
+    return hipGetLastError();
+}
+
+}  // namespace ta

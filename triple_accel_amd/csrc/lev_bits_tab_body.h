@@ -1,0 +1,253 @@
+// lev_bits_tab_body.h -- the TABLE form of the bit-parallel band kernel's stride-8 LINE form (lev_bits_body.h): the same band of up to 33
+// diagonals, the same line fetch (parked lines, one piece of each string committed per 16 columns, rings of 3 + 2 pieces), the same
+// 12-operation recurrence, bottom diagonal, zero-step count and way down -- but the match vector PM comes out of two per-pair nibble
+// tables in LDS instead of 32 byte compares and a gather tree.  Levenshtein only (no transposition term), fixed-length batches.
+//
+// Tables.  Per wavefront TL[16][64] and TH[16][64] dwords, [entry][lane] (8 KB, at the start of the wavefront's LDS): bank = lane for
+// any per-lane entry, so no access conflicts.  The window's 32 rows sit in 32 ring SLOTS: the row that iteration t inserts (string
+// offset t - ca) owns slot t & 31.  INVARIANT: bit s of TL[v][lane] is set iff the row in slot s has low nibble v; TH likewise for the
+// high nibble.  TL[b & 15] & TH[b >> 4] is then the exact match mask in slot coordinates (both bits belong to the same slot, hence the
+// same row: nibbles of different rows cannot combine), and the window word -- bit i = the row i below the window's top -- is that
+// mask rotated right by the top row's slot, t & 31 at iteration t: a compile-time amount, because the column loop is unrolled over the
+// 32 iterations of two 16-column spans (T0 is a multiple of 64).
+// Sliding.  After column t's lookup the top row leaves and the row iteration t inserts (this column's bottom diagonal, still a byte
+// compare) takes its slot: bit t & 31 is flipped (ds_xor, one data register) in TL[lo(old)], TH[hi(old)], TL[lo(new)], TH[hi(new)];
+// equal nibbles cancel.  `old` is the very dword `new` was 32 iterations ago: the eight dwords of `a` read for the last 32 iterations
+// stay in registers (F, a ring of names: no moves), so the byte that clears a slot is the byte that set it whatever the rings held --
+// rows above row 1 and below row a_len included, which need no masking here either (lev_bits_body.h, header).
+// Ordering.  A wavefront's LDS operations execute in order and every lane touches only its own column of the tables: lookup t, four
+// flips, lookup t + 1 needs no barrier.  All of them depend on string bytes only, so column t + 1's lookup is issued before column t's
+// recurrence and its latency sits under VALU work.
+// Addresses.  lane * 4 | nibble << 8 (+ 4096 as the instruction's offset for TH): ONE SDWA instruction per address writes the nibble of the selected
+// byte into byte 1 of a register that holds lane * 4 (T::nib_to_byte1, both addresses of a byte in one call; T = the table form's own operations, wave_tab.h).  They are ABSOLUTE LDS addresses
+// (T::lds_abs_read32 / lds_abs_xor32): `lds` must be the start of the block's LDS, address 0 -- one wavefront per block, no static LDS.
+// Per column: 6 address instructions, 1 AND, 1 rotate, 12 of the recurrence and the bottom diagonal's 2 VALU; 2 LDS reads, 4 LDS xors.
+#pragma once
+#include <type_traits>
+
+#include "bitop3.h"
+#include "lev_band_body.h"
+
+namespace ta {
+
+// what the host emulation's driver hooks in to check the invariant (tests/emu_tab); the kernels take this one: nothing
+struct TabNoProbe {
+    template <class U32> static TA_HD inline void block(const uint8_t *, const U32 (&)[8], uint32_t) {}
+};
+
+constexpr uint32_t LEV_TAB_TABLE_BYTES = 8192u;                                  // TL at 0, TH at 4096
+constexpr uint32_t LEV_TAB_SLOT_A = 52u, LEV_TAB_SLOT_B = 36u;                   // rings of 3 and 2 pieces + 4 bytes of wrap copy
+constexpr uint32_t LEV_TAB_LDS_PER_WAVE = LEV_TAB_TABLE_BYTES + 64u * (LEV_TAB_SLOT_A + LEV_TAB_SLOT_B);   // 13,824 bytes: 11 wavefronts per CU
+
+template <class W, class T, class PROBE = TabNoProbe>
+struct LevBitsTab {
+    using U32 = typename W::U32;
+    using Bool = typename W::Bool;
+    using Ptr = typename W::Ptr;
+    using Q = typename W::Q;
+    static constexpr int WB = 33;
+
+    struct State {
+        U32 VP, VN;             // vertical +1 / -1 differences of the previous column, window bits 0..31 (the 33rd diagonal: lev_bits_body.h, ONEBIT)
+        U32 acc;                // D0 of the window's top diagonal, the last columns' bits from bit 31 down
+        U32 F[8];               // the dwords of `a` of the last 32 iterations: dword (t >> 2) & 7 holds iteration t's byte in byte t & 3
+        U32 aLL, aLH;           // table addresses (byte 0 = lane * 4, byte 1 = the nibble): the lookup's,
+        U32 aOL, aOH, aNL, aNH; // the leaving row's and the entering row's
+        U32 mL, mH;             // the lookup in flight: TL[b & 15], TH[b >> 4] of the next column
+    };
+
+    // table entries of the column character, byte C of b_dw
+    template <int C>
+    static TA_HD inline __attribute__((always_inline)) void lookup(State &st, const uint8_t *lds, const U32 &b_dw) {
+        T::template nib_to_byte1<C>(st.aLL, st.aLH, b_dw);
+        st.mL = T::lds_abs_read32(lds, st.aLL);
+        st.mH = T::lds_abs_read32(lds, st.aLH + 4096u);
+    }
+
+    // iteration t with t & 31 == S: byte S & 3 of a_new enters slot S (COLUMN: byte S & 3 of F[S >> 2] leaves it), then column t - T0 + 1 runs on
+    // the lookup issued a step ago.  NEXT: issue the next column's lookup (byte (S + 1) & 3 of b_next) behind this iteration's flips.
+    template <int S, bool COLUMN, bool NEXT>
+    static TA_HD inline __attribute__((always_inline)) void step(State &st, uint8_t *lds, const U32 &a_new, const U32 &b_dw, const U32 &b_next) {
+        constexpr int C = S & 3;
+        const U32 mL = st.mL, mH = st.mH;
+        const U32 bit = W::splat(1u << S);
+        if (COLUMN) {
+            T::template nib_to_byte1<C>(st.aOL, st.aOH, st.F[S >> 2]);
+            T::lds_abs_xor32(lds, st.aOL, bit);
+            T::lds_abs_xor32(lds, st.aOH + 4096u, bit);
+        }
+        T::template nib_to_byte1<C>(st.aNL, st.aNH, a_new);
+        T::lds_abs_xor32(lds, st.aNL, bit);
+        T::lds_abs_xor32(lds, st.aNH + 4096u, bit);
+        if (COLUMN && NEXT) lookup<(S + 1) & 3>(st, lds, b_next);
+        if (COLUMN) {
+            const U32 m = mL & mH;
+            U32 PM;
+            if constexpr (S == 0) PM = m; else PM = W::template alignbit<(S ? S : 1)>(m, m);
+            // the recurrence of lev_bits_body.h, step8 (no transposition term), operation by operation
+            const U32 pv = PM & st.VP;
+            U32 sum;
+            const typename W::Mask cm = W::add_carry_mask(pv, st.VP, sum);
+            const U32 X = bitop3<0xBE>(sum, st.VP, PM);                 // (sum ^ VP) | PM
+            const U32 D0 = X | st.VN;
+            const U32 d0_bot = W::template byte_eq_or<C>(a_new, b_dw, cm);   // the 33rd diagonal: match | carry, in bit 0
+            const U32 HP = bitop3<0xF1>(st.VN, X, st.VP);               // VN | ~(X | VP)
+            const U32 HN = X & st.VP;
+            st.acc = W::template alignbit<1>(D0, st.acc);
+            const U32 D0s = W::template alignbit<1>(d0_bot, D0);
+            st.VP = bitop3<0xF1>(HN, D0s, HP);                          // HN | ~(D0s | HP)
+            st.VN = D0s & HP;
+        }
+        if (C == 3) st.F[S >> 2] = a_new;
+    }
+
+    // 16 iterations tb .. tb + 15, tb & 31 == 16 PH; r[g] / bw[g] = the dwords of `a` / `b` of iterations tb + 4 g .. + 3.  TAIL: only the
+    // first `left` (1..16) of them run (the columns end inside the span)
+    template <int PH, bool COLUMN, bool TAIL>
+    static TA_HD inline __attribute__((always_inline)) void span(State &st, uint8_t *lds, const U32 (&r)[4], const U32 (&bw)[4], uint32_t left) {
+        if (COLUMN) lookup<0>(st, lds, bw[0]);
+#define TA_TAB_STEP(I)                                                                                                   \
+        if (!TAIL || left > (uint32_t)(I)) {                                                                             \
+            if (TAIL && left == (uint32_t)(I) + 1u) step<16 * PH + (I), COLUMN, false>(st, lds, r[(I) >> 2], bw[(I) >> 2], bw[((I) + 1) >> 2 & 3]); \
+            else step<16 * PH + (I), COLUMN, ((I) < 15)>(st, lds, r[(I) >> 2], bw[(I) >> 2], bw[((I) + 1) >> 2 & 3]);    \
+        }
+        TA_TAB_STEP(0) TA_TAB_STEP(1) TA_TAB_STEP(2) TA_TAB_STEP(3) TA_TAB_STEP(4) TA_TAB_STEP(5) TA_TAB_STEP(6) TA_TAB_STEP(7)
+        TA_TAB_STEP(8) TA_TAB_STEP(9) TA_TAB_STEP(10) TA_TAB_STEP(11) TA_TAB_STEP(12) TA_TAB_STEP(13) TA_TAB_STEP(14) TA_TAB_STEP(15)
+#undef TA_TAB_STEP
+    }
+
+    static TA_HD inline void run(const LevParams &P, uint32_t wave_index, uint8_t *lds) {
+        const U32 lane = W::lane();
+        const U32 slot_idx = lane + wave_index * 64u;
+        const Bool valid = slot_idx < P.n;
+        const U32 pair = P.subset ? W::load_u32(P.subset, slot_idx, valid, 0u) : slot_idx;
+        const Bool active = (lane == lane);
+
+        Ptr aptr, bptr;
+        U32 alen, blen;
+        W::load_str(P.a, pair, valid, aptr, alen);     // rows (a lane without a pair points at the batch's first pair; its bytes go nowhere)
+        W::load_str(P.b, pair, valid, bptr, blen);     // columns
+
+        // the batch's band (lev_plan.h): diagonals d = j - i in [-nlo, d_hi]; window bit i <-> diagonal d_hi - i.  One geometry per wavefront.
+        const uint32_t alen_u = (uint32_t)P.a.len, blen_u = (uint32_t)P.b.len;
+        const uint32_t diff_u = blen_u >= alen_u ? blen_u - alen_u : alen_u - blen_u;
+        const bool inband = diff_u <= P.u;                  // else None (src/levenshtein.rs:426-428)
+        const uint32_t nlo_u = inband ? ((P.u - diff_u) >> 1) + (blen_u >= alen_u ? 0u : diff_u) : 0u;
+        const uint32_t dhi_u = (uint32_t)WB - 1u - nlo_u;
+        const uint32_t idx_ans = inband ? (dhi_u + alen_u) - blen_u : 0u;   // row a_len at column b_len
+
+        State st;
+        {
+            // column 0, D[r][0] = |r|: rows r = 1 - d_hi + i >= 1 step up (+1), rows <= 0 step down (-1)
+            const uint32_t below = dhi_u >= 32u ? 0xFFFFFFFFu : ((1u << dhi_u) - 1u);
+            st.VN = W::splat(below);
+            st.VP = W::splat(~below);
+        }
+        st.acc = W::splat(0);
+        st.mL = W::splat(0); st.mH = W::splat(0);
+#pragma unroll
+        for (int i = 0; i < 8; i++) st.F[i] = W::splat(0);
+        st.aLL = st.aLH = st.aOL = st.aOH = st.aNL = st.aNH = lane << 2;
+        U32 cnt = W::splat(0);
+        uint32_t nacc = 0;                                     // columns whose bits (the top nacc of st.acc) are not counted yet, <= 32
+        auto flush = [&]() { cnt = W::bcnt(st.acc >> (32u - nacc), cnt); nacc = 0; };      // (nacc >= 1)
+
+        // iteration tp inserts a[tp - ca_s] into the window and, from tp = T0 on, runs column tp - T0 + 1 with b[tp - T0]
+        const uint32_t T0 = P.Tw;                              // a multiple of 64 (lev_plan.h)
+        const int32_t ca_s = (int32_t)T0 - (int32_t)nlo_u;
+        const uint32_t iters = T0 + blen_u;
+
+        // ---- the LINE fetch of lev_bits_body.h: every 128-byte line of a string requested once, whole, parked in registers and handed to
+        // LDS piece by piece; string offsets before the string are pieces < 0, delivered as zeros
+        constexpr int32_t RA = 3, RB = 2;
+        const U32 a_slot = lane * LEV_TAB_SLOT_A + LEV_TAB_TABLE_BYTES, b_slot = lane * LEV_TAB_SLOT_B + (LEV_TAB_TABLE_BYTES + 64u * LEV_TAB_SLOT_A);
+        Q SA[8], SB[8];
+        auto fetch_a = [&](int32_t m) {
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                const int32_t off = 128 * m + 16 * c;
+                const Bool ok = (off >= 0 && (uint32_t)off < alen_u) ? active : W::bfalse();
+                SA[c] = W::gload16(W::ptr_add(aptr, W::splat(off >= 0 ? (uint32_t)off : 0u)), ok);
+            }
+        };
+        auto fetch_b = [&](int32_t m) {
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                const int32_t off = 128 * m + 16 * c;
+                const Bool ok = (off >= 0 && (uint32_t)off < blen_u) ? active : W::bfalse();
+                SB[c] = W::gload16(W::ptr_add(bptr, W::splat(off >= 0 ? (uint32_t)off : 0u)), ok);
+            }
+        };
+        auto put = [&](const Q (&S)[8], int32_t piece, U32 dst, uint32_t wrap_copy_at) {     // wrap_copy_at: 0 = none
+            switch (piece & 7) {                                   // wave-uniform: one of eight stores
+#define TA_PUT(c) case c: { W::lds_store16(lds, dst, S[c], active); if (wrap_copy_at) W::lds_write32(lds, dst + wrap_copy_at, W::qword(S[c], 0)); } break;
+                TA_PUT(0) TA_PUT(1) TA_PUT(2) TA_PUT(3) TA_PUT(4) TA_PUT(5) TA_PUT(6) TA_PUT(7)
+#undef TA_PUT
+            }
+        };
+        auto fmod = [](int32_t x, int32_t m) -> uint32_t { const int32_t r = x % m; return (uint32_t)(r < 0 ? r + m : r); };
+        auto commit_a = [&](int32_t piece) {
+            const uint32_t slot = fmod(piece, RA);
+            put(SA, piece, a_slot + 16u * slot, slot == 0u ? 16u * RA : 0u);
+            if ((piece & 7) == 7) fetch_a((piece >> 3) + 1);
+        };
+        auto commit_b = [&](int32_t piece) {
+            const uint32_t slot = fmod(piece, RB);
+            put(SB, piece, b_slot + 16u * slot, slot == 0u ? 16u * RB : 0u);
+            if ((piece & 7) == 7) fetch_b((piece >> 3) + 1);
+        };
+
+        // the warm-up: the tables zeroed (eight 16-byte stores per lane cover the 8 KB), then the 32 iterations in front of the first column
+        // insert the first window's rows -- whatever bytes the ring holds for them (zeros above row 1)
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; i++) W::lds_store16(lds, (lane << 4) + 1024u * i, W::qzero(), active);
+        const uint32_t tb0 = T0 - 32u;
+        int32_t qa = ((int32_t)tb0 - ca_s) >> 4, qb = ((int32_t)tb0 - (int32_t)T0) >> 4;
+        fetch_a(qa >> 3);
+        fetch_b(qb >> 3);
+        for (int32_t x = qa; x < qa + RA - 1; x++) commit_a(x);
+        for (int32_t x = qb; x < qb + RB - 1; x++) commit_b(x);
+
+        // one block: a piece of each string into the slot of the piece the last block finished, then its 16 iterations
+        auto block = [&](uint32_t tb, auto phase_tag) {
+            constexpr int PH = decltype(phase_tag)::value;
+            commit_a(qa + RA - 1);
+            commit_b(qb + RB - 1);
+            qa++; qb++;
+            W::lds_wave_sync();
+            U32 r[4], bw[4];
+#pragma unroll
+            for (uint32_t g = 0; g < 4u; g++) {
+                r[g] = W::lds_read32u(lds, a_slot + fmod((int32_t)(tb + 4u * g) - ca_s, 16 * RA));
+                bw[g] = W::lds_read32u(lds, b_slot + fmod((int32_t)(tb + 4u * g) - (int32_t)T0, 16 * RB));
+            }
+            if (tb < T0) {
+                span<PH, false, false>(st, lds, r, bw, 16u);
+            } else {
+                PROBE::block(lds, st.F, tb);
+                if (tb + 16u <= iters) {
+                    span<PH, true, false>(st, lds, r, bw, 16u);
+                    nacc += 16u;
+                } else {
+                    span<PH, true, true>(st, lds, r, bw, iters - tb);
+                    nacc += iters - tb;
+                }
+                if (PH == 1 || tb + 16u >= iters) flush();
+            }
+        };
+        for (uint32_t tb = tb0; tb < iters; tb += 32u) {
+            block(tb, std::integral_constant<int, 0>());
+            if (tb + 16u >= iters) break;
+            block(tb + 16u, std::integral_constant<int, 1>());
+        }
+
+        // the way down from the top diagonal's cell to row a_len: idx_ans steps over the last column's vertical differences
+        const uint32_t mb = idx_ans >= 32u ? 0xFFFFFFFFu : ((1u << idx_ans) - 1u);
+        const U32 tail = W::bcnt(st.VP & mb, W::splat(0)) - W::bcnt(st.VN & mb, W::splat(0));
+        const U32 d = (W::splat(dhi_u) + blen) - cnt + tail;   // the top diagonal starts at d_hi; + columns - zero-difference steps + way down
+        const Bool some = (d <= P.k) & (W::splat(inband ? 1u : 0u) != 0u);        // :539-541
+        W::store_u32(P.out, pair, W::sel(some, d, W::splat(0xFFFFFFFFu)), valid);
+    }
+};
+
+}  // namespace ta

@@ -194,6 +194,20 @@ static inline LevBits2Plan lev_bits2_make_plan(uint32_t k, uint32_t mc, uint32_t
     return p;
 }
 
+// ---- table form of the stride-8 line form (lev_bits_tab_body.h): the match vector from two per-pair nibble tables in LDS.  Its domain is
+// the stride-8 LINE form's Levenshtein case -- no transposition term, a fixed-length batch in the line form of the fetch (strings longer
+// than one 128-byte line), no checkpoints, no early out, a pair count the host knows; costs that are multiples of the unit costs arrive
+// here as unit costs (lev_unit_scale).  The route takes it from LEV_BITS_TAB_MIN_PAIRS pairs on: 8 KB of tables per wavefront leave 11
+// wavefronts per CU instead of 16, which a launch has to be big enough to fill anyway.
+constexpr uint32_t LEV_BITS_TAB_MIN_PAIRS = 262144;
+static inline bool lev_bits_tab_in_domain(const LevBitsPlan &pl, bool has_t, bool line_form, uint64_t max_len) {
+    return pl.ok && pl.s8 && !has_t && line_form && max_len > 128u && (pl.Tw & 63u) == 0u;
+}
+// force: TA_FORCE_TAB_FORM (any pair count inside the domain); never: TA_NO_TAB_FORM
+static inline bool lev_bits_tab_applies(const LevBitsPlan &pl, bool has_t, bool line_form, uint64_t max_len, uint64_t pairs, bool force, bool never) {
+    return lev_bits_tab_in_domain(pl, has_t, line_form, max_len) && !never && (force || pairs >= LEV_BITS_TAB_MIN_PAIRS);
+}
+
 // ---- score form of the DP band kernel (lev_band_body.h, SCORE): the cells hold gc (i+j) - dp, so the substitution adds the byte
 // 2 gc - mc [a != b]: both bytes must be in 0..255, and so must the transposition's 4 gc - tc (>= 0 always: tc / 2 < gc).
 // trans: 0 none, 1 dot4 penalty, 2 select form (cost form only).

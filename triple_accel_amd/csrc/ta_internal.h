@@ -148,6 +148,14 @@ bool tuning_enabled();
 const char *env_str(const char *name);
 int env_int(const char *name);
 
+// The table form's host rule (its pure half: lev_bits_tab_applies, lev_plan.h): a launch of the stride-8 line form without transposition
+// term, checkpoints, early out or a device-side pair count, of at least LEV_BITS_TAB_MIN_PAIRS pairs.  Under TA_TUNING,
+// TA_FORCE_TAB_FORM=1 takes it at any pair count inside its domain and TA_NO_TAB_FORM=1 never takes it.
+static inline bool tab_form_wanted(const LevParams &P, const LevBitsPlan &pl, bool trans, bool line_form, bool early, uint64_t max_len) {
+    if (early || P.ckpt || P.n_dev) return false;
+    return lev_bits_tab_applies(pl, trans, line_form, max_len, P.n, env_int("TA_FORCE_TAB_FORM") != 0, env_int("TA_NO_TAB_FORM") != 0);
+}
+
 // ta_set_option(TA_OPT_EARLY_OUT) of the calling thread
 bool early_out_enabled();
 bool unit_prefilter_enabled();
@@ -165,6 +173,8 @@ hipError_t lev_band_trace_batch_launch(const LevParams &P, const LevPlan &pl, bo
                                        uint64_t cap, uint32_t *path, uint32_t path_words, hipStream_t s);
 hipError_t lev_bits_launch(const LevParams &P, const LevBitsPlan &pl, bool trans, uint64_t max_len, hipStream_t s,
                            uint32_t *grid_out, uint32_t *lds_out);
+// the table form of the stride-8 line form (lev_bits_tab.hip): what lev_bits_launch hands the batches tab_form_wanted() names
+hipError_t lev_bits_tab_launch(const LevParams &P, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out);
 // the VLINE fetch form (lev_bits_vline.hip): CSR batches through the stride-8 window
 hipError_t lev_bits_vline_launch(const LevParams &P, const LevBitsPlan &pl, bool trans, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out);
 hipError_t lev_bitsq_launch(const LevParams &P, bool trans, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out);
