@@ -55,21 +55,21 @@ enum ScratchSlot {
                              // search_dev_core): no search entry runs a distance pass.
     SLOT_LINES = 6,          // what ONE kernel of a pass needs beside its inputs: the stripe boundary lines of lev_wide.hip / lev_widebits.hip (every
                              // launcher there; lev_pass runs one of them per pass, the exp loop's passes follow each other on the stream), those of
-                             // trace_widebits, the memory-backed columns of ta_search.hip (needles beyond 32 bytes) and the DP band kernel's
-                             // traceback records (ta_levenshtein_trace, the record route of ta_levenshtein_trace_batch: neither runs a lev_wide /
+                             // trace_widebits (ta_trace.hip), the memory-backed columns of ta_search.hip (needles beyond 32 bytes) and the DP band kernel's
+                             // traceback records (ta_trace.hip: ta_levenshtein_trace, the record route of ta_levenshtein_trace_batch: neither runs a lev_wide /
                              // lev_widebits launcher; the token entries' wide pass follows the byte pass on the stream).
-    SLOT_AUX_A = 7,          // ta_search.hip: the needle's device copy (needles beyond 32 / 64 bytes) | trace_bits_batch: the run counts.
+    SLOT_AUX_A = 7,          // ta_search.hip: the needle's device copy (needles beyond 32 / 64 bytes) | ta_trace.hip, trace_bits_batch: the run counts.
     SLOT_AUX_B = 8,          // lev_widebits.hip: the tiled form's stripe states (4 and 5 hold the exp loop's subsets while it runs) | trace_bits_batch:
                              // the run lists -- ensured after its distance pass (lev_pass, which may take the tiled form) has been enqueued.
-    SLOT_TRACE = 9,          // traceback records of one pair (trace_widebits, trace_wide, ta_tokens.hip: wide_pair_u32) | trace_bits_batch: the
+    SLOT_TRACE = 9,          // traceback records of one pair (ta_trace.hip: trace_widebits, trace_wide; ta_tokens.hip: wide_pair_u32) | trace_bits_batch: the
                              // checkpoints | the record route of ta_levenshtein_trace_batch: the walked paths.  One route per call; the packed form's
                              // sub-batches are calls of their own, one after the other.
     SLOT_EXP_BOUND = 10,     // ta_levenshtein_exp_batch: the bag lower bounds ...
     SLOT_EXP_WORK = 11,      // ... and the list of pairs a bounded round takes.  Alone.
     SLOT_SELECT = 12,        // ta_search.hip: a Best pass's SearchSlots, then (after the pass's synchronisation) best_hits_of's selection |
-                             // ta_levenshtein_trace_batch_packed: the ta_edit records of a sub-batch, live across the inner record-route call
+                             // ta_trace.hip, ta_levenshtein_trace_batch_packed: the ta_edit records of a sub-batch, live across the inner record-route call
                              // (which uses 6 and 9).
-    SLOT_ORDER = 13,         // order_pairs for the distance entries (ta_levenshtein_k_batch, _exp_batch, trace_bits_batch): the length-ordered list,
+    SLOT_ORDER = 13,         // order_pairs for the distance entries (ta_levenshtein_k_batch, _exp_batch; ta_trace.hip: trace_bits_batch): the length-ordered list,
     SLOT_ORDER_BINS = 14,    // read until the call's last pass, and its histogram -- persists (zero between complete passes; Scratch::bins_clean).
     SLOT_ALPHA_BAD = 15,     // ta_levenshtein_k_batch_alphabet: the pairs with a byte outside the alphabet ...
     SLOT_ALPHA_COUNT = 16,   // ... and the two counters taken in turn -- persists.  Alone.
@@ -101,6 +101,18 @@ static inline uint32_t costs_scale(const ta_edit_costs *c) {   // 1: unit family
     return lev_cost_scale(c->mismatch_cost, c->gap_cost, c->start_gap_cost, c->has_transpose != 0, c->transpose_cost);
 }
 static inline StrView view_of(const ta_strings *s) { return StrView{s->blob, s->off, s->stride, s->len}; }
+// the strings lo.. of a batch side as a side of their own (sub-batches); max_len: the whole side's bound, as the CSR form's
+static inline ta_strings strings_slice(const ta_strings *s, uint64_t lo, uint64_t max_len) {
+    return s->off ? ta_strings{s->blob, s->off + lo, 0, 0, max_len} : ta_strings{s->blob + lo * s->stride, nullptr, s->stride, s->len, s->len};
+}
+static inline ta_edit_costs unit_costs(bool trans) {       // LEVENSHTEIN_COSTS, or RDAMERAU_COSTS with the transposition term
+    return ta_edit_costs{1, 1, 0, (uint8_t)(trans ? 1 : 0), (uint8_t)(trans ? 1 : 0)};
+}
+static inline uint32_t launch_cell_bits(uint64_t max_len, uint32_t k, const ta_edit_costs *c) {   // ta_launch_info.cell_bits of a batch
+    ta_lev_select sel;
+    ta_levenshtein_select((size_t)max_len, (size_t)max_len, k, c, &sel);
+    return sel.cell_bits;
+}
 // the length bound of a batch side: known without measuring (strided, or CSR with max_len given), and its value
 static inline bool side_bound_known(const ta_strings *s) { return !s->off || s->max_len; }
 static inline uint64_t side_bound(const ta_strings *s) { return s->off ? s->max_len : s->len; }
@@ -131,6 +143,23 @@ struct CallCtx {
     void release();
 };
 CallCtx &call_ctx();
+
+// What the traceback entries (ta_trace.hip) share with the distance entries (ta_api.hip, where the comments are).  Staged: one (a, b)
+// pair of a single call as stage_pair leaves it and fetch_u32 reads its answer back.
+constexpr uint32_t TA_SLOT_EMPTY = 0xFFFFFFFEu;    // "no answer yet": distances stay below 0xFFFFFFF0, None is 0xFFFFFFFF
+struct Staged {
+    ta_strings sa, sb;
+    uint32_t *out_dev;             // where the kernel writes
+    volatile uint32_t *out_host;   // host view of out_dev (pinned case) or nullptr
+    hipStream_t st;
+};
+int stage_pair(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, Staged *S);
+int fetch_u32(const Staged &S, uint32_t *out, bool single_store = false);
+int lev_pass(const ta_strings *a, const ta_strings *b, uint32_t n_work, const uint32_t *subset, uint32_t k, const ta_edit_costs *c,
+             uint64_t max_len, uint32_t *out_dev, hipStream_t st, bool columns_ordered = false, const uint32_t *n_dev = nullptr);
+int batch_max_len(const ta_strings *a, const ta_strings *b, uint32_t n, hipStream_t st, uint64_t *out);
+bool stream_is_capturing(hipStream_t s);
+ta_launch_info &last_launch();     // the calling thread's record behind ta_last_launch_info
 
 // The batch / *_dev entry points run on the CALLER's stream but keep state in thread-local scratch that their kernels may
 // still be using when the call returns.  A later call from the same thread on a DIFFERENT stream first makes that stream

@@ -6,11 +6,12 @@
 // The cost check, the batch argument check and the scratch slots' names (SLOT_TOK_*) are the shared ones of ta_internal.h.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
-#include <string.h>
 
+#include <optional>
 #include <unordered_map>
 #include <vector>
 
+#include "lev_script.h"
 #include "sym_compact_body.h"
 #include "ta_internal.h"
 
@@ -117,10 +118,10 @@ static int tok_overflow_pass(const ta_tokens *a, const ta_tokens *b, size_t n, u
     return TA_OK;
 }
 
-// One pair of u32 items on the device through the wide kernel: distance, and with `res` the script (x = the shorter side on the rows,
-// as src/levenshtein.rs:386-390).  Host inputs; synchronises.
+// One pair of u32 items on the device through the wide kernel: distance, and with `res` the finished script in (*res)->runs (x = the shorter
+// side on the rows, as src/levenshtein.rs:386-390; `*res` is set unless the answer is None).  Host inputs; synchronises.
 static int wide_pair_u32(const uint32_t *a, size_t la, const uint32_t *b, size_t lb, uint32_t k, const ta_edit_costs *costs, hipStream_t st,
-                         uint32_t *out, std::vector<ta_edit> *res) {
+                         uint32_t *out, std::optional<ScriptBuilder<uint32_t>> *res) {
     const bool swap = res && la > lb;
     const uint32_t *x = swap ? b : a, *y = swap ? a : b;
     const size_t n = swap ? lb : la, m = swap ? la : lb;
@@ -146,27 +147,9 @@ static int wide_pair_u32(const uint32_t *a, size_t la, const uint32_t *b, size_t
     std::vector<uint32_t> tr((size_t)code_words);
     TA_HIP(hipMemcpyAsync(tr.data(), ts.dev, (size_t)code_words * 4, hipMemcpyDeviceToHost, st));
     TA_HIP(hipStreamSynchronize(st));
-    res->clear();
-    size_t i = n, j = m;
-    while (i > 0 || j > 0) {                                                    // :561-603 (as ta_api.hip, trace_wide)
-        uint32_t code;
-        if (i == 0) code = 1;
-        else if (j == 0) code = 2;
-        else {
-            const size_t q = (i - 1) / 2048, r = (i - 1) % 2048, lane = r / 32, rr = r % 32;
-            code = (tr[((q * tcols + j) * 64 + lane) * 2 + (rr >> 4)] >> (2 * (rr & 15))) & 3u;
-        }
-        uint32_t e;
-        switch (code) {
-            case 0: i--; j--; e = (x[i] == y[j]) ? TA_EDIT_MATCH : TA_EDIT_MISMATCH; break;
-            case 1: j--; e = swap ? TA_EDIT_BGAP : TA_EDIT_AGAP; break;
-            case 2: i--; e = swap ? TA_EDIT_AGAP : TA_EDIT_BGAP; break;
-            default: i -= 2; j -= 2; e = TA_EDIT_TRANSPOSE; break;
-        }
-        if (!res->empty() && res->back().edit == e) res->back().count++;
-        else res->push_back(ta_edit{e, 0u, 1u});
-    }
-    for (size_t t = 0; t < res->size() / 2; t++) std::swap((*res)[t], (*res)[res->size() - 1 - t]);   // :605 reverse
+    ScriptBuilder<uint32_t> &walk = res->emplace(x, n, y, m, swap);
+    while (walk.i() > 0 || walk.j() > 0) walk.step(wide_trace_code(tr.data(), tcols, walk.i(), walk.j()));   // :561-603
+    walk.finish();
     return TA_OK;
 }
 
@@ -257,7 +240,7 @@ int ta_levenshtein_trace_batch_tokens(const ta_tokens *a, const ta_tokens *b, si
     TA_HIP(hipMemcpyAsync(list.data(), C.ovf_list, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
     TA_HIP(hipStreamSynchronize(st));
     std::vector<uint32_t> xa, xb;
-    std::vector<ta_edit> res;
+    std::optional<ScriptBuilder<uint32_t>> res;                              // (set by wide_pair_u32 unless the answer is None)
     for (uint32_t p : list) {
         const ta_tokens *sd[2] = {a, b};
         std::vector<uint32_t> *buf[2] = {&xa, &xb};
@@ -272,11 +255,11 @@ int ta_levenshtein_trace_batch_tokens(const ta_tokens *a, const ta_tokens *b, si
         TA_HIP(hipStreamSynchronize(st));
         uint32_t d = 0;
         if ((rc = wide_pair_u32(xa.data(), xa.size(), xb.data(), xb.size(), k, costs, st, &d, &res))) return rc;
-        const uint32_t ne = d == TA_NONE ? 0u : (uint32_t)res.size();
+        const uint32_t ne = d == TA_NONE ? 0u : (uint32_t)res->runs.size();
         TA_HIP(hipMemcpyAsync(out_dev + p, &d, 4, hipMemcpyHostToDevice, st));
         TA_HIP(hipMemcpyAsync(n_edits_dev + p, &ne, 4, hipMemcpyHostToDevice, st));
         const size_t keep = ne < cap ? ne : cap;
-        if (keep) TA_HIP(hipMemcpyAsync(edits_dev + (size_t)p * cap, res.data(), keep * sizeof(ta_edit), hipMemcpyHostToDevice, st));
+        if (keep) TA_HIP(hipMemcpyAsync(edits_dev + (size_t)p * cap, res->runs.data(), keep * sizeof(ta_edit), hipMemcpyHostToDevice, st));
         TA_HIP(hipStreamSynchronize(st));                                      // (the host buffers are reused)
     }
     return TA_OK;
@@ -297,15 +280,9 @@ int ta_levenshtein_tokens(const uint32_t *a, size_t a_len, const uint32_t *b, si
     if (rc) return rc;
     hipStream_t st = call_ctx().st;
     if (!edits) return wide_pair_u32(a, a_len, b, b_len, k, costs, st, out, nullptr);
-    std::vector<ta_edit> res;
+    std::optional<ScriptBuilder<uint32_t>> res;
     if ((rc = wide_pair_u32(a, a_len, b, b_len, k, costs, st, out, &res))) return rc;
-    if (*out != TA_NONE && !res.empty()) {
-        *edits = (ta_edit *)malloc(res.size() * sizeof(ta_edit));
-        if (!*edits) return TA_ERR_ARG;
-        memcpy(*edits, res.data(), res.size() * sizeof(ta_edit));
-        *n_edits = res.size();
-    }
-    return TA_OK;
+    return *out == TA_NONE ? TA_OK : res->release(edits, n_edits);
 }
 
 }  // extern "C"
