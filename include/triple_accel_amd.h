@@ -395,6 +395,52 @@ int ta_hamming_cross(const ta_strings *queries, size_t nq, const ta_strings *tar
                      uint64_t *nearest_dev    /* nq entries, or NULL */,
                      uint32_t *per_query_dev  /* nq entries, or NULL */, void *stream);
 
+/* Every needle of a panel searched in every haystack of a batch within k, on device-resident data: the shape a demultiplexer or an
+ * adapter trimmer asks for -- 12 adapters, 96 sample barcodes, a primer set against a batch of reads: which needle occurs where in every
+ * read (no reference analogue: the reference searches one needle in one haystack per call, src/levenshtein.rs:1911-1966).  The two cross
+ * entries above compare whole strings, the search-batch entries take one needle per haystack.
+ * For needle p and haystack i let R(p, i) be the list ta_levenshtein_search_simd_with_opts(needle p, haystack i, k, TA_SEARCH_BEST, costs,
+ * anchored) returns: the reference's Best result -- the end == 0 match (:1693-1706), the empty-needle answers (:1919-1963), the overlap
+ * fold (:1812-1835), quirk Q2 -- with positions relative to haystack i.  The pair is a hit exactly when R is not empty; its record is
+ * {haystack = i, needle = p, start = R[0].start, end = R[0].end, k = R[0].k, n_matches = len(R)}.  Best mode only: there is no
+ * search_type argument.
+ * *count_dev and hits_dev[0 .. min(count, cap)) follow ta_levenshtein_cross's rules word for word: the count is the exact number of hits
+ * whatever `cap` is, the kept records are distinct true hits in no particular order (an atomic cursor), cap = 0 asks for the count only
+ * and hits_dev may then be NULL.  nearest_dev[i], when not NULL, is the smallest (uint64_t)R[0].k << 32 | p over the hits of haystack
+ * i -- the cheapest needle, at equal cost the lowest needle index -- and all ones when haystack i has no hit.  best_dev[i], when not NULL,
+ * is that needle's R[0] as a ta_match with pad_ = 0, or {0, 0, TA_NONE, 0} when there is no hit; it may be asked for without nearest_dev
+ * (the library then keeps the nearest words in its own scratch).  per_haystack_dev[i], when not NULL, is the number of needles that hit
+ * haystack i: with nearest_dev it answers "best needle per read, and is it the only one within k?".  None of the three depends on cap.
+ * Nothing of size nn x nh is allocated or written by the caller, and the library's own scratch is bounded: the candidate pairs of at
+ * most 256 MB worth of haystacks at a time (sub-batches of whole workgroups on the same stream).
+ * Both sides take the strided and the CSR form at any byte alignment and follow the TA_BLOB_SLACK rule; every layout freedom listed
+ * above ta_strings applies.  Limits, TA_ERR_UNSUPPORTED: every NEEDLE is at most 32 bytes -- a longer bound (the strided len, the CSR
+ * max_len given or measured) is unsupported, the exact kernel's register form goes no further; nn is at most 65,535 (the needle groups
+ * are the grid's y dimension); a haystack of 2^32 bytes or more, or nh >= 2^32.
+ * Errors, all before any device work, in the search-batch entries' order: TA_ERR_ARG for NULL costs / needles / haystacks / count_dev;
+ * TA_ERR_BAD_COSTS when EditCosts::new or check_search fails (:1965), decided for the whole call; TA_ERR_ARG for a NULL blob with
+ * nn, nh > 0, cap > 0 with NULL hits_dev, cap * sizeof(ta_search_cross_hit) overflowing; the limits above; no device: TA_ERR_HIP.
+ * nn == 0 or nh == 0: TA_OK, the count zero, every nearest word all ones, every per-haystack count zero, every best {0, 0, TA_NONE, 0}.
+ * The call enqueues its work on `stream` and returns without synchronising; the counter and the three per-haystack outputs are
+ * initialised by kernels.  With every length bound known (strided sides, CSR max_len given on both) it is capturable under the rule
+ * above (run once outside the capture first; the number of sub-batches depends on nn and nh only); a CSR side with max_len = 0 costs one
+ * synchronisation to measure it.  Routes: a bit-parallel unit-cost scan of every haystack against 64 needles per wavefront (a superset
+ * filter under any EditCosts), then the exact recurrence on the candidate pairs' spans; anchored: the exact recurrence on every pair's
+ * prefix.  ta_last_kernel_name names the scan kernel, lev_search_cross_scan_kernel<TRANS>, or the exact kernel
+ * lev_search_cross_exact_kernel<N, TRANS, PACKED> when the call is anchored. */
+typedef struct {
+    uint32_t haystack, needle;   /* indices */
+    uint32_t start, end;         /* R[0] of the pair, relative to the haystack */
+    uint32_t k;                  /* R[0].k */
+    uint32_t n_matches;          /* len(R) */
+} ta_search_cross_hit;
+int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                uint32_t k, const ta_edit_costs *costs, int anchored,
+                                ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                uint64_t *nearest_dev      /* nh entries, or NULL */,
+                                ta_match *best_dev         /* nh entries, or NULL */,
+                                uint32_t *per_haystack_dev /* nh entries, or NULL */, void *stream);
+
 /* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
  * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
  * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of

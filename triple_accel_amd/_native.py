@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "ta_levenshtein_search_batch", "ta_hamming_search_batch",
     # every query against every target (ta_cross.hip)
     "ta_levenshtein_cross", "ta_hamming_cross",
+    # every needle of a panel in every haystack (ta_cross.hip)
+    "ta_levenshtein_search_cross",
 ]
 
 TA_CROSS_UPPER = 1          # ta_hamming_cross flags: only pairs with target index > query index
@@ -66,6 +68,11 @@ class LaunchInfoC(C.Structure):
 
 class CrossHitC(C.Structure):
     _fields_ = [("query", C.c_uint32), ("target", C.c_uint32), ("k", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class SearchCrossHitC(C.Structure):
+    _fields_ = [("haystack", C.c_uint32), ("needle", C.c_uint32), ("start", C.c_uint32), ("end", C.c_uint32), ("k", C.c_uint32),
+                ("n_matches", C.c_uint32)]
 
 
 class StringsC(C.Structure):
@@ -194,6 +201,7 @@ def lib():
     sig("ta_hamming_search_batch", i32, [sp, sp, sz, u32, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     sig("ta_levenshtein_cross", i32, [sp, sz, sp, sz, u32, cp, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p])
     sig("ta_hamming_cross", i32, [sp, sz, sp, sz, u32, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("ta_levenshtein_search_cross", i32, [sp, sz, sp, sz, u32, cp, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     _lib = L
     return L
 

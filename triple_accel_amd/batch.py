@@ -554,3 +554,51 @@ def cross_to_arrays(hits, count, allow_cut=False):
     order = np.lexsort((h[:, 1], h[:, 0]))
     h = h[order]
     return h[:, 0].copy(), h[:, 1].copy(), h[:, 2].copy()
+
+
+def levenshtein_search_cross(needles: Strings, haystacks: Strings, k, costs=LEVENSHTEIN_COSTS, anchored=False, cap=None, hits=None, count=None,
+                             nearest=False, best=False, per_haystack=False):
+    """Every needle of a panel searched in every haystack within k, on the device (ta_levenshtein_search_cross): -> (hits, count, nearest,
+    best, per_haystack).  For needle p and haystack i let R = levenshtein_search_simd_with_opts(needle p, haystack i, k, SearchType.Best,
+    costs, anchored): the pair is a hit exactly when R is not empty.  count (int64, one element) = the number of hits whatever cap is;
+    hits[:min(count, cap)] = that many distinct hits as int32 (haystack, needle, R[0].start, R[0].end, R[0].k, len(R)) rows in no
+    particular order (search_cross_to_arrays sorts them).  cap = 0: the count only.  nearest = True (or an int64 tensor of haystacks.n
+    elements to reuse): nearest[i] = R[0].k << 32 | p of haystack i's cheapest needle -- at equal cost the lowest index -- and -1 where no
+    needle hits.  best = True (or an int64 (haystacks.n, 3) tensor): that needle's R[0] as a (start, end, k) row, (0, 0, 0xFFFFFFFF) where
+    no needle hits; it does not need nearest.  per_haystack = True (or an int32 tensor): the number of needles that hit haystack i.  None
+    of the three depends on cap; each is None when not asked for.  Needles of at most 32 bytes, at most 65,535 of them.  Default cap: room
+    for eight hits per haystack (at least 1,024, at most every pair).  Nothing is synchronised: read count before trusting hits."""
+    nn, nh, dev = needles.n, haystacks.n, haystacks.blob.device
+    if cap is None:
+        cap = hits.numel() // 6 if hits is not None else min(nn * nh, max(1024, 8 * nh))
+    hits = torch.empty((cap, 6), dtype=torch.int32, device=dev) if hits is None else hits
+    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+    nearest = torch.empty(nh, dtype=torch.int64, device=dev) if nearest is True else None if nearest is False else nearest
+    best = torch.empty((nh, 3), dtype=torch.int64, device=dev) if best is True else None if best is False else best
+    per_haystack = torch.empty(nh, dtype=torch.int32, device=dev) if per_haystack is True else None if per_haystack is False else per_haystack
+    assert hits.dtype == torch.int32 and hits.is_contiguous() and hits.numel() >= cap * 6
+    assert count.dtype == torch.int64 and count.numel() >= 1
+    assert nearest is None or (nearest.dtype == torch.int64 and nearest.is_contiguous() and nearest.numel() >= nh)
+    assert best is None or (best.dtype == torch.int64 and best.is_contiguous() and best.numel() >= nh * 3)
+    assert per_haystack is None or (per_haystack.dtype == torch.int32 and per_haystack.is_contiguous() and per_haystack.numel() >= nh)
+    cc = _costs(costs)._c()
+    rc = _n.lib().ta_levenshtein_search_cross(needles._ref(), nn, haystacks._ref(), nh, int(k), _C.byref(cc), int(bool(anchored)),
+                                              hits.data_ptr() if cap else None, count.data_ptr(), cap,
+                                              None if nearest is None else nearest.data_ptr(), None if best is None else best.data_ptr(),
+                                              None if per_haystack is None else per_haystack.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return hits, count, nearest, best, per_haystack
+
+
+def search_cross_to_arrays(hits, count, allow_cut=False):
+    """the device result of levenshtein_search_cross as numpy arrays (haystack, needle, start, end, k, n_matches), sorted by (haystack,
+    needle) (host copy).  More hits than the `cap` rows of `hits` were cut on the device (count says how many there are): that is an
+    error here, not a silently shorter result, unless the caller asks for the cut one (allow_cut)."""
+    import numpy as np
+    n, cap = int(count.cpu()[0].item()), hits.shape[0]
+    if n > cap and not allow_cut:
+        raise ValueError("search cross: %d hits for cap = %d records; pass a larger cap" % (n, cap))
+    h = hits[:min(n, cap)].cpu().numpy().view(np.uint32).reshape(-1, 6)
+    h = h[np.lexsort((h[:, 1], h[:, 0]))]
+    return tuple(h[:, c].copy() for c in range(6))

@@ -1,10 +1,13 @@
-// ta_cross.hip -- ta_levenshtein_cross and ta_hamming_cross (include/triple_accel_amd.h): validation, the length
-// bounds, the query tile and the launch of lev_cross.hip / ham_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
+// ta_cross.hip -- ta_levenshtein_cross, ta_hamming_cross and ta_levenshtein_search_cross (include/triple_accel_amd.h; DESIGN.md 3.13, 3.14,
+// 3.15): validation, the length bounds, the query tile / the sub-batches and the launches of lev_cross.hip / ham_cross.hip /
+// lev_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
 // there is no synchronisation and the call can be captured into a graph.  The shared host rules (cost check and scale, length bounds,
-// measured maxima) and the scratch slot's name (SLOT_CROSS_CTL) are those of ta_internal.h; the query tile's rule is lev_plan.h's cross_qtile.
+// measured maxima) and the scratch slots' names (SLOT_CROSS_CTL, SLOT_SX_*) are those of ta_internal.h; the query tile's rule is
+// lev_plan.h's cross_qtile, the sub-batches' lev_search_cross_body.h's sx_plan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lev_search_cross_body.h"
 #include "ta_internal.h"
 
 namespace ta {
@@ -42,6 +45,14 @@ static int cross_fill64(unsigned long long *p, uint32_t half, uint64_t n, hipStr
         TA_HIP(fill_u32_launch(w + done, half, (uint32_t)part, st));
         done += part;
     }
+    return TA_OK;
+}
+
+// ta_levenshtein_search_cross's limits over the counts and the length bounds known so far (0: not known yet)
+static int search_cross_limits(uint64_t nn, uint64_t nh, uint64_t max_needle, uint64_t max_hay) {
+    if (max_needle > SX_MAX_NEEDLE) { set_last_error_msg("search cross: a needle longer than 32 bytes"); return TA_ERR_UNSUPPORTED; }
+    if (nn > 65535u) { set_last_error_msg("search cross: more than 65,535 needles"); return TA_ERR_UNSUPPORTED; }
+    if (max_hay >> 32 || nh >> 32) { set_last_error_msg("search cross: a haystack of 2^32 bytes or more, or 2^32 or more haystacks"); return TA_ERR_UNSUPPORTED; }
     return TA_OK;
 }
 
@@ -112,5 +123,77 @@ extern "C" int ta_hamming_cross(const ta_strings *queries, size_t nq, const ta_s
     // The query tile, as ta_levenshtein_cross sizes it, in whole staging chunks (lev_plan.h: cross_qtile)
     P.qtile = cross_qtile(nq, nt, 0, chunk, env_int("TA_HCROSS_QTILE"));
     TA_HIP(ham_cross_launch(P, nw, st));
+    return TA_OK;
+}
+
+extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                           uint32_t k, const ta_edit_costs *costs, int anchored,
+                                           ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                           uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+    if (!costs || !needles || !haystacks || !count_dev) { set_last_error_msg("null costs / needles / haystacks / count_dev"); return TA_ERR_ARG; }
+    if (!costs_ok(costs) || ta_edit_costs_check_search(costs) != TA_OK) return TA_ERR_BAD_COSTS;   // EditCosts::new; :1965, for the whole call
+    if (nn && nh && (!needles->blob || !haystacks->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
+    if (cap && !hits_dev) { set_last_error_msg("cap > 0 with null hits_dev"); return TA_ERR_ARG; }
+    if (cap > SIZE_MAX / sizeof(ta_search_cross_hit)) { set_last_error_msg("cap * sizeof(ta_search_cross_hit) overflows"); return TA_ERR_ARG; }
+    int rc = search_cross_limits(nn, nh, side_bound_known(needles) ? side_bound(needles) : 0, side_bound_known(haystacks) ? side_bound(haystacks) : 0);
+    if (rc) return rc;
+    if (!device_ready()) return TA_ERR_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard guard(st);
+    // the nearest words: the caller's, or the library's own when only best_dev is asked for
+    unsigned long long *nearest = (unsigned long long *)nearest_dev;
+    if (!nearest && best_dev && nh) {
+        Scratch &ns = tls_scratch(SLOT_SX_NEAR);
+        if ((rc = ns.ensure(nh * sizeof(unsigned long long)))) return rc;
+        nearest = (unsigned long long *)ns.dev;
+    }
+    if ((rc = cross_fill64(count_dev, 0u, 1, st))) return rc;
+    if (nearest && (rc = cross_fill64(nearest, 0xFFFFFFFFu, nh, st))) return rc;
+    if (per_haystack_dev && nh) TA_HIP(fill_u32_launch(per_haystack_dev, 0u, (uint32_t)nh, st));
+    if (best_dev) TA_HIP(search_cross_init_best_launch(best_dev, (uint32_t)nh, st));
+    if (nn == 0 || nh == 0) return TA_OK;
+    Scratch &ctl = tls_scratch(SLOT_SX_CTL);
+    if ((rc = ctl.ensure(64))) return rc;
+    uint64_t max_n = 0, max_h = 0;
+    if ((rc = measure_max_lens(needles, (uint32_t)nn, haystacks, (uint32_t)nh, (unsigned long long *)ctl.dev + 2, st, &max_n, &max_h))) return rc;
+    if ((rc = search_cross_limits(nn, nh, max_n, max_h))) return rc;
+
+    SearchCrossParams P = {};
+    P.nd = view_of(needles); P.hs = view_of(haystacks);
+    P.nn = (uint32_t)nn;
+    P.k = k; P.mc = costs->mismatch_cost; P.gc = costs->gap_cost; P.sg = costs->start_gap_cost;
+    P.tc = costs->has_transpose ? costs->transpose_cost : 0;
+    P.anchored = anchored ? 1u : 0u;
+    P.max_needle = (uint32_t)max_n;
+    const bool trans = costs->has_transpose != 0;
+    // the scan's threshold and the packed form's conditions: ta_levenshtein_search_batch's (ta_search_batch.hip)
+    P.kf = costs_unit(costs) ? k : srch_filter_k(k, P.mc, P.gc, P.sg, trans, P.tc);
+    const uint64_t halo = max_n + P.kf + 2;                                             // (only needles with kf < n <= 32 use it)
+    P.halo = halo > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)halo;
+    const uint32_t unit_k = lev_sat_sub(k, P.sg) / P.gc;
+    const uint64_t cols = anchored ? (max_h < max_n + unit_k ? max_h : max_n + unit_k) : max_h;
+    bool packed = !needles->off && max_n >= 1 && max_n <= 32 && k <= 30000u && cols <= 60000u && !env_int("TA_SEARCH_BATCH_UNPACKED");
+    if (anchored) packed = packed && srch_anchored_packed_ok(cols, (uint32_t)max_n, P.mc, P.gc, P.sg);
+    P.hits = hits_dev; P.cap = cap; P.count = count_dev; P.nearest = nearest; P.per_haystack = per_haystack_dev; P.best = best_dev;
+
+    // Sub-batches of whole workgroups: the records of one stay within SX_BUDGET; their number depends on nn, nh and the budget only
+    const int forced = env_int("TA_SEARCH_CROSS_SUB");
+    const SxPlan plan = sx_plan(nn, nh, forced > 0 ? (uint64_t)forced : 0);
+    Scratch &rs = tls_scratch(SLOT_SX_REC);
+    if ((rc = rs.ensure((size_t)plan.sub * nn * sizeof(SxRec)))) return rc;
+    P.rec = (SxRec *)rs.dev;
+    P.hpw = plan.hpw;
+    P.n_rec = anchored ? nullptr : (uint32_t *)ctl.dev;
+    for (uint64_t h0 = 0; h0 < nh; h0 += plan.sub) {
+        P.h0 = (uint32_t)h0;
+        P.h1 = (uint32_t)(h0 + plan.sub < nh ? h0 + plan.sub : nh);
+        if (!anchored) {
+            TA_HIP(fill_u32_launch(P.n_rec, 0u, 1, st));
+            TA_HIP(search_cross_scan_launch(P, trans, st));
+        }
+        TA_HIP(search_cross_exact_launch(P, trans, packed, st));
+        TA_HIP(search_cross_finish_launch(P, st));
+    }
+    if (!anchored) set_last_kernel_name("lev_search_cross_scan_kernel<%s>", trans ? "true" : "false");
     return TA_OK;
 }

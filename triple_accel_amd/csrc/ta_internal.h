@@ -86,6 +86,9 @@ enum ScratchSlot {
     SLOT_SB_SPAN = 27,       // ... and their spans.
     SLOT_SB_COL = 28,        // the memory-backed columns (needles beyond 32 bytes).  23..28: the search batch alone.
     SLOT_CROSS_CTL = 30,     // ta_cross.hip: measure_max_lens' two 64-bit words.  Alone.
+    SLOT_SX_CTL = 31,        // ta_levenshtein_search_cross: word 0 the candidate count of the sub-batch in flight; words 4..7: measure_max_lens.
+    SLOT_SX_REC = 32,        // ... the candidate / result records of one sub-batch (at most SX_BUDGET bytes),
+    SLOT_SX_NEAR = 33,       // ... and the nearest words when the caller asks for best_dev without nearest_dev.  31..33: that entry alone.
     TA_SCRATCH_SLOTS
 };
 Scratch &tls_scratch(ScratchSlot which);
@@ -382,6 +385,30 @@ struct HamCrossParams {
     uint32_t *per_query;          // device: nq words pre-zeroed, or nullptr
 };
 hipError_t ham_cross_launch(const HamCrossParams &P, int nw, hipStream_t st);
+
+// ta_levenshtein_search_cross (lev_search_cross.hip): every needle of a panel in every haystack, one sub-batch of haystacks per launch
+struct SxRec;
+struct SearchCrossParams {
+    StrView nd, hs;               // needles (every one at most 32 bytes), haystacks
+    uint32_t nn;
+    uint32_t h0, h1;              // the sub-batch: haystacks [h0, h1)
+    uint32_t hpw;                 // haystacks per scan workgroup
+    uint32_t k, mc, gc, sg, tc, anchored;
+    uint32_t kf, halo;            // the scan's threshold, the exact pass's left context
+    uint32_t max_needle;          // bound on every needle's length (the packed form: every needle's length)
+    SxRec *rec;                   // device: the sub-batch's records (scan: the candidate list; anchored: one per (haystack, needle))
+    uint32_t *n_rec;              // device: the list's length (pre-zeroed), or nullptr: anchored, (h1 - h0) * nn records
+    ta_search_cross_hit *hits;    // device: cap records, or nullptr with cap = 0
+    uint64_t cap;
+    unsigned long long *count;    // device, pre-zeroed
+    unsigned long long *nearest;  // device: nh words preset to all ones, or nullptr
+    uint32_t *per_haystack;       // device: nh words pre-zeroed, or nullptr
+    ta_match *best;               // device: nh records preset to {0, 0, TA_NONE, 0}, or nullptr
+};
+hipError_t search_cross_init_best_launch(ta_match *best, uint32_t nh, hipStream_t st);
+hipError_t search_cross_scan_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
+hipError_t search_cross_exact_launch(const SearchCrossParams &P, bool trans, bool packed, hipStream_t st);
+hipError_t search_cross_finish_launch(const SearchCrossParams &P, hipStream_t st);
 
 // ta_multi.hip: the device set (one worker thread per entry).  multi_search_shards / multi_pair_shards: over how many of them a host
 // haystack / a host batch of that size is spread (1: the calling thread's own device path).  The search forms return the All-mode hits
