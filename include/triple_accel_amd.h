@@ -441,6 +441,47 @@ int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn, const ta_s
                                 ta_match *best_dev         /* nh entries, or NULL */,
                                 uint32_t *per_haystack_dev /* nh entries, or NULL */, void *stream);
 
+/* Every needle of a panel searched in every haystack of a batch within k MISMATCHES, on device-resident data: the Hamming twin of
+ * ta_levenshtein_search_cross, for panels designed around a minimum Hamming distance -- sample barcodes behind staggers, inline indices,
+ * primers -- where "at most k mismatches, no indels" is the rule (at k = 1 the Levenshtein entry also accepts a shifted tag, and its
+ * start, end and k differ).  A tag at a KNOWN offset is ta_hamming_cross over a strided view; this entry finds it at any offset (no
+ * reference analogue: the reference searches one needle in one haystack per call, src/hamming.rs:454-475, scalar text :96-146).
+ * For needle p and haystack i let R(p, i) be the list ta_hamming_search_simd_with_opts(needle p, haystack i, k, TA_SEARCH_BEST) returns:
+ * the windows at the smallest mismatch count <= k, in increasing start, no overlap fold (:105-142).  The pair is a hit exactly when R is
+ * not empty; its record is {haystack = i, needle = p, start = R[0].start, end = R[0].start + needle_len, k = R[0].k, n_matches = len(R)}.
+ * Best mode only: there is no search_type argument.  k is any uint32_t: k >= needle_len makes every window a candidate, Best then reports
+ * the windows at the minimum and n_matches can be haystack_len - needle_len + 1.
+ * *count_dev, hits_dev[0 .. min(count, cap)), cap = 0, nearest_dev, best_dev and per_haystack_dev follow ta_levenshtein_search_cross word
+ * for word: the count is the exact number of hits whatever `cap` is, the kept records are distinct true hits in no particular order,
+ * cap = 0 asks for the count only and hits_dev may then be NULL; nearest_dev[i] is the smallest (uint64_t)R[0].k << 32 | p over the hits
+ * of haystack i, all ones when there is none; best_dev[i] is that needle's R[0] with pad_ = 0, or {0, 0, TA_NONE, 0}, and may be asked
+ * for without nearest_dev; per_haystack_dev[i] is the number of needles that hit haystack i.  None of the three depends on cap.
+ * The reference's checks keep their order per pair (:455-461): needle_len > haystack_len, then needle_len == 0, give no hit -- an empty
+ * needle never hits, unlike the Levenshtein entry.  Only then the NUL rule applies: in a haystack that holds a 0x00 byte the pairs with
+ * 1 <= needle_len <= haystack_len, where the single call returns TA_ERR_NULL_BYTE, produce no record and touch neither nearest nor
+ * best, and per_haystack_dev[i] = TA_NONE when at least one such pair exists; the call still returns TA_OK and every other haystack is
+ * unaffected (ta_hamming_search_batch's convention).  A caller who cannot rule out 0x00 bytes asks for per_haystack_dev.  A NUL in a
+ * needle, in the bytes around the strings, or in a haystack shorter than every non-empty needle is not an error.
+ * Both sides take the strided and the CSR form at any byte alignment and follow the TA_BLOB_SLACK rule; every layout freedom listed
+ * above ta_strings applies.  Limits, TA_ERR_UNSUPPORTED: every NEEDLE is at most 32 bytes -- a longer bound (the strided len, the CSR
+ * max_len given or measured) is unsupported, the counters are one dword wide; nn is at most 65,535 (the needle groups are the grid's y
+ * dimension); a haystack of 2^32 bytes or more, or nh >= 2^32.
+ * Errors, all before any device work, in this order: TA_ERR_ARG for NULL needles / haystacks / count_dev; TA_ERR_ARG for a NULL blob
+ * with nn, nh > 0, cap > 0 with NULL hits_dev, cap * sizeof(ta_search_cross_hit) overflowing; the limits above; no device: TA_ERR_HIP.
+ * nn == 0 or nh == 0: TA_OK, the count zero, every nearest word all ones, every per-haystack count zero, every best {0, 0, TA_NONE, 0}.
+ * The call enqueues its work on `stream` and returns without synchronising; every output is initialised by kernels.  With every length
+ * bound known (strided sides, CSR max_len given on both) it is capturable under the rule above (run once outside the capture first); a
+ * CSR side with max_len = 0 costs one synchronisation to measure it.  One pass, exact: bit-sliced mismatch counters of every haystack
+ * against 64 needles per wavefront -- no candidate list, no scratch of size nn x nh, no sub-batches (the library keeps one 64-bit word
+ * per haystack when nearest_dev or best_dev is asked for).  ta_last_kernel_name names the scan kernel with its plane count,
+ * ham_search_cross_kernel<B>, B = the smallest with 2^B - 1 >= min(k, longest needle): 1 .. 6. */
+int ta_hamming_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                            uint32_t k,
+                            ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                            uint64_t *nearest_dev      /* nh entries, or NULL */,
+                            ta_match *best_dev         /* nh entries, or NULL */,
+                            uint32_t *per_haystack_dev /* nh entries, or NULL */, void *stream);
+
 /* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
  * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
  * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of

@@ -468,6 +468,45 @@ def levenshtein_search_nearest_many(needles, haystacks, k, costs=LEVENSHTEIN_COS
             (int(w) & 0xFFFFFFFF, Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF), int(c)) for w, r, c in zip(words, rows, counts)]
 
 
+def _hsx_panic(per):
+    """ta_hamming_search_cross marks a haystack where a single call would panic with a count of TA_NONE"""
+    nul = [i for i, c in enumerate(per) if int(c) == 0xFFFFFFFF]
+    if nul:
+        raise PanicError("No zero/null bytes allowed in the string! (haystack %d)" % nul[0])
+
+
+def hamming_search_cross_many(needles, haystacks, k):
+    """Every needle searched in every haystack in ONE device call (ta_hamming_search_cross): the sorted list of (haystack, needle, Match,
+    n_matches) for every pair where R = hamming_search_simd_with_opts(needles[p], haystacks[i], k, SearchType.Best) is not empty, with
+    Match = R[0] and n_matches = len(R).  Raises PanicError where a single call would (a NUL byte in a haystack that is not shorter than
+    some non-empty needle).  Needles of at most 32 bytes.  Both lists are uploaded; when there are more hits than the first call's room,
+    one more call runs with room for the count it reported."""
+    from . import batch as B
+    nd, hs = _cross_sides(needles, haystacks)
+    k = _k(k)
+    hits, count, _, _, per = B.hamming_search_cross(nd, hs, k, per_haystack=True)
+    n = int(count.cpu()[0].item())
+    if n > hits.shape[0]:
+        hits, count, _, _, per = B.hamming_search_cross(nd, hs, k, cap=n, per_haystack=True)
+    _hsx_panic(per.cpu().numpy().view("uint32"))
+    cols = B.search_cross_to_arrays(hits, count)
+    return [(int(i), int(p), Match(int(s), int(e), int(d)), int(m)) for i, p, s, e, d, m in zip(*cols)]
+
+
+def hamming_search_nearest_many(needles, haystacks, k):
+    """For every haystack its needle with the fewest mismatches within k, where it matches and how many needles hit, in ONE device call
+    (ta_hamming_search_cross, counting only): a list of (needle index | None, Match | None, needles that hit) -- the smallest R[0].k, at
+    equal count the lowest needle index.  needles that hit == 1 is the demultiplexer's "exactly one barcode within k mismatches".
+    Raises PanicError where a single call would."""
+    from . import batch as B
+    nd, hs = _cross_sides(needles, haystacks)
+    _, _, nearest, best, per = B.hamming_search_cross(nd, hs, _k(k), cap=0, nearest=True, best=True, per_haystack=True)
+    words, rows, counts = nearest.cpu().numpy().view("uint64"), best.cpu().numpy(), per.cpu().numpy().view("uint32")
+    _hsx_panic(counts)
+    return [(None, None, 0) if int(w) == 0xFFFFFFFFFFFFFFFF else
+            (int(w) & 0xFFFFFFFF, Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF), int(c)) for w, r, c in zip(words, rows, counts)]
+
+
 def levenshtein_select(a_len, b_len, k, costs=LEVENSHTEIN_COSTS):
     """The dispatcher arithmetic (src/levenshtein.rs:731-791): (max_k, unit_k, cell_bits, ref_lanes)."""
     s = _n.LevSelectC()

@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     # every query against every target (ta_cross.hip)
     "ta_levenshtein_cross", "ta_hamming_cross",
     # every needle of a panel in every haystack (ta_cross.hip)
-    "ta_levenshtein_search_cross",
+    "ta_levenshtein_search_cross", "ta_hamming_search_cross",
 ]
 
 TA_CROSS_UPPER = 1          # ta_hamming_cross flags: only pairs with target index > query index
@@ -202,6 +202,7 @@ def lib():
     sig("ta_levenshtein_cross", i32, [sp, sz, sp, sz, u32, cp, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p])
     sig("ta_hamming_cross", i32, [sp, sz, sp, sz, u32, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("ta_levenshtein_search_cross", i32, [sp, sz, sp, sz, u32, cp, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("ta_hamming_search_cross", i32, [sp, sz, sp, sz, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     _lib = L
     return L
 

@@ -602,3 +602,34 @@ def search_cross_to_arrays(hits, count, allow_cut=False):
     h = hits[:min(n, cap)].cpu().numpy().view(np.uint32).reshape(-1, 6)
     h = h[np.lexsort((h[:, 1], h[:, 0]))]
     return tuple(h[:, c].copy() for c in range(6))
+
+
+def hamming_search_cross(needles: Strings, haystacks: Strings, k, cap=None, hits=None, count=None, nearest=False, best=False, per_haystack=False):
+    """Every needle of a panel searched in every haystack within k MISMATCHES, on the device (ta_hamming_search_cross): -> (hits, count,
+    nearest, best, per_haystack), shaped as levenshtein_search_cross's (search_cross_to_arrays reads hits and count).  For needle p and
+    haystack i let R = hamming_search_simd_with_opts(needle p, haystack i, k, SearchType.Best): the pair is a hit exactly when R is not
+    empty, its row is (haystack, needle, R[0].start, R[0].end, R[0].k, len(R)).  An empty needle never hits.  Where the single call
+    panics -- a NUL byte in a haystack that is not shorter than the non-empty needle -- the pair has no row and touches neither nearest
+    nor best, and per_haystack[i] = -1 for such a haystack: a caller who cannot rule out NUL bytes asks for per_haystack.  The other
+    haystacks are unaffected.  Needles of at most 32 bytes, at most 65,535 of them.  Default cap: room for eight hits per haystack (at
+    least 1,024, at most every pair).  Nothing is synchronised: read count before trusting hits."""
+    nn, nh, dev = needles.n, haystacks.n, haystacks.blob.device
+    if cap is None:
+        cap = hits.numel() // 6 if hits is not None else min(nn * nh, max(1024, 8 * nh))
+    hits = torch.empty((cap, 6), dtype=torch.int32, device=dev) if hits is None else hits
+    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+    nearest = torch.empty(nh, dtype=torch.int64, device=dev) if nearest is True else None if nearest is False else nearest
+    best = torch.empty((nh, 3), dtype=torch.int64, device=dev) if best is True else None if best is False else best
+    per_haystack = torch.empty(nh, dtype=torch.int32, device=dev) if per_haystack is True else None if per_haystack is False else per_haystack
+    assert hits.dtype == torch.int32 and hits.is_contiguous() and hits.numel() >= cap * 6
+    assert count.dtype == torch.int64 and count.numel() >= 1
+    assert nearest is None or (nearest.dtype == torch.int64 and nearest.is_contiguous() and nearest.numel() >= nh)
+    assert best is None or (best.dtype == torch.int64 and best.is_contiguous() and best.numel() >= nh * 3)
+    assert per_haystack is None or (per_haystack.dtype == torch.int32 and per_haystack.is_contiguous() and per_haystack.numel() >= nh)
+    rc = _n.lib().ta_hamming_search_cross(needles._ref(), nn, haystacks._ref(), nh, int(k), hits.data_ptr() if cap else None,
+                                          count.data_ptr(), cap, None if nearest is None else nearest.data_ptr(),
+                                          None if best is None else best.data_ptr(),
+                                          None if per_haystack is None else per_haystack.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return hits, count, nearest, best, per_haystack

@@ -1,12 +1,13 @@
-// ta_cross.hip -- ta_levenshtein_cross, ta_hamming_cross and ta_levenshtein_search_cross (include/triple_accel_amd.h; DESIGN.md 3.13, 3.14,
-// 3.15): validation, the length bounds, the query tile / the sub-batches and the launches of lev_cross.hip / ham_cross.hip /
-// lev_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
+// ta_cross.hip -- ta_levenshtein_cross, ta_hamming_cross, ta_levenshtein_search_cross and ta_hamming_search_cross
+// (include/triple_accel_amd.h): validation, the length bounds, the query tile / the sub-batches and the launches of
+// lev_cross.hip / ham_cross.hip / lev_search_cross.hip / ham_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
 // there is no synchronisation and the call can be captured into a graph.  The shared host rules (cost check and scale, length bounds,
 // measured maxima) and the scratch slots' names (SLOT_CROSS_CTL, SLOT_SX_*) are those of ta_internal.h; the query tile's rule is
 // lev_plan.h's cross_qtile, the sub-batches' lev_search_cross_body.h's sx_plan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ham_search_cross_body.h"
 #include "lev_search_cross_body.h"
 #include "ta_internal.h"
 
@@ -48,7 +49,7 @@ static int cross_fill64(unsigned long long *p, uint32_t half, uint64_t n, hipStr
     return TA_OK;
 }
 
-// ta_levenshtein_search_cross's limits over the counts and the length bounds known so far (0: not known yet)
+// the limits of ta_levenshtein_search_cross and ta_hamming_search_cross over the counts and the length bounds known so far (0: not known yet)
 static int search_cross_limits(uint64_t nn, uint64_t nh, uint64_t max_needle, uint64_t max_hay) {
     if (max_needle > SX_MAX_NEEDLE) { set_last_error_msg("search cross: a needle longer than 32 bytes"); return TA_ERR_UNSUPPORTED; }
     if (nn > 65535u) { set_last_error_msg("search cross: more than 65,535 needles"); return TA_ERR_UNSUPPORTED; }
@@ -195,5 +196,51 @@ extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn,
         TA_HIP(search_cross_finish_launch(P, st));
     }
     if (!anchored) set_last_kernel_name("lev_search_cross_scan_kernel<%s>", trans ? "true" : "false");
+    return TA_OK;
+}
+
+extern "C" int ta_hamming_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                       uint32_t k,
+                                       ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                       uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+    if (!needles || !haystacks || !count_dev) { set_last_error_msg("null needles / haystacks / count_dev"); return TA_ERR_ARG; }
+    if (nn && nh && (!needles->blob || !haystacks->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
+    if (cap && !hits_dev) { set_last_error_msg("cap > 0 with null hits_dev"); return TA_ERR_ARG; }
+    if (cap > SIZE_MAX / sizeof(ta_search_cross_hit)) { set_last_error_msg("cap * sizeof(ta_search_cross_hit) overflows"); return TA_ERR_ARG; }
+    int rc = search_cross_limits(nn, nh, side_bound_known(needles) ? side_bound(needles) : 0, side_bound_known(haystacks) ? side_bound(haystacks) : 0);
+    if (rc) return rc;
+    if (!device_ready()) return TA_ERR_HIP;
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard guard(st);
+    if ((rc = cross_fill64(count_dev, 0u, 1, st))) return rc;
+    if (per_haystack_dev && nh) TA_HIP(fill_u32_launch(per_haystack_dev, 0u, (uint32_t)nh, st));
+    if (nn == 0 || nh == 0) {
+        if (nearest_dev && (rc = cross_fill64((unsigned long long *)nearest_dev, 0xFFFFFFFFu, nh, st))) return rc;
+        if (best_dev) TA_HIP(search_cross_init_best_launch(best_dev, (uint32_t)nh, st));
+        return TA_OK;
+    }
+    Scratch &ctl = tls_scratch(SLOT_HSX_CTL);
+    if ((rc = ctl.ensure(64))) return rc;
+    uint64_t max_n = 0, max_h = 0;
+    if ((rc = measure_max_lens(needles, (uint32_t)nn, haystacks, (uint32_t)nh, (unsigned long long *)ctl.dev, st, &max_n, &max_h))) return rc;
+    if ((rc = search_cross_limits(nn, nh, max_n, max_h))) return rc;
+
+    HamSearchCrossParams P = {};
+    P.nd = view_of(needles); P.hs = view_of(haystacks);
+    P.nn = (uint32_t)nn; P.nh = (uint32_t)nh;
+    P.kc = hsx_threshold(k, (uint32_t)max_n);
+    P.hits = hits_dev; P.cap = cap; P.count = count_dev; P.per_haystack = per_haystack_dev;
+    P.nearest = (unsigned long long *)nearest_dev; P.best = best_dev;
+    // the packed nearest words: every haystack's minimum over its hits, unpacked into nearest_dev / best_dev by the finish kernel
+    if (nearest_dev || best_dev) {
+        Scratch &ws = tls_scratch(SLOT_HSX_WORD);
+        if ((rc = ws.ensure(nh * sizeof(unsigned long long)))) return rc;
+        P.packed = (unsigned long long *)ws.dev;
+        if ((rc = cross_fill64(P.packed, 0xFFFFFFFFu, nh, st))) return rc;
+    }
+    const int forced = env_int("TA_HSEARCH_CROSS_HPW");
+    P.hpw = hsx_hpw(nn, nh, forced > 0 ? (uint64_t)forced : 0);
+    TA_HIP(ham_search_cross_launch(P, st));                                          // (names the kernel: ham_search_cross_kernel<B>)
+    TA_HIP(ham_search_cross_finish_launch(P, st));
     return TA_OK;
 }

@@ -89,6 +89,9 @@ enum ScratchSlot {
     SLOT_SX_CTL = 31,        // ta_levenshtein_search_cross: word 0 the candidate count of the sub-batch in flight; words 4..7: measure_max_lens.
     SLOT_SX_REC = 32,        // ... the candidate / result records of one sub-batch (at most SX_BUDGET bytes),
     SLOT_SX_NEAR = 33,       // ... and the nearest words when the caller asks for best_dev without nearest_dev.  31..33: that entry alone.
+    SLOT_HSX_CTL = 34,       // ta_hamming_search_cross: measure_max_lens' two 64-bit words ...
+    SLOT_HSX_WORD = 35,      // ... and the packed nearest words (d << 48 | needle << 32 | start), one per haystack, live from the fill to the
+                             // finish kernel.  34, 35: that entry alone.
     TA_SCRATCH_SLOTS
 };
 Scratch &tls_scratch(ScratchSlot which);
@@ -409,6 +412,23 @@ hipError_t search_cross_init_best_launch(ta_match *best, uint32_t nh, hipStream_
 hipError_t search_cross_scan_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
 hipError_t search_cross_exact_launch(const SearchCrossParams &P, bool trans, bool packed, hipStream_t st);
 hipError_t search_cross_finish_launch(const SearchCrossParams &P, hipStream_t st);
+
+// ta_hamming_search_cross (ham_search_cross.hip): every needle of a panel in every haystack, substitutions only, in one launch
+struct HamSearchCrossParams {
+    StrView nd, hs;               // needles (every one at most 32 bytes), haystacks
+    uint32_t nn, nh;
+    uint32_t hpw;                 // haystacks per workgroup
+    uint32_t kc;                  // min(k, longest needle): the counters' threshold (ham_search_cross_body.h: hsx_threshold)
+    ta_search_cross_hit *hits;    // device: cap records, or nullptr with cap = 0
+    uint64_t cap;
+    unsigned long long *count;    // device, pre-zeroed
+    unsigned long long *packed;   // device: nh packed words preset to all ones, or nullptr: neither nearest nor best is asked for
+    uint32_t *per_haystack;       // device: nh words pre-zeroed, or nullptr
+    unsigned long long *nearest;  // device: nh words the finish kernel writes, or nullptr
+    ta_match *best;               // device: nh records the finish kernel writes, or nullptr
+};
+hipError_t ham_search_cross_launch(const HamSearchCrossParams &P, hipStream_t st);
+hipError_t ham_search_cross_finish_launch(const HamSearchCrossParams &P, hipStream_t st);
 
 // ta_multi.hip: the device set (one worker thread per entry).  multi_search_shards / multi_pair_shards: over how many of them a host
 // haystack / a host batch of that size is spread (1: the calling thread's own device path).  The search forms return the All-mode hits
