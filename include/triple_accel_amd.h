@@ -395,6 +395,28 @@ int ta_hamming_cross(const ta_strings *queries, size_t nq, const ta_strings *tar
                      uint64_t *nearest_dev    /* nq entries, or NULL */,
                      uint32_t *per_query_dev  /* nq entries, or NULL */, void *stream);
 
+/* ta_levenshtein_cross with queries of up to 256 bytes and ta_hamming_cross's two further outputs: short reads against each other or a
+ * panel, amplicons, dictionary lines, a read or UMI set de-duplicated within a few edits.  The hit rule, *count_dev, hits_dev, cap,
+ * nearest_dev and the costs accepted are ta_levenshtein_cross's word for word; per_query_dev and flags = TA_CROSS_UPPER are
+ * ta_hamming_cross's word for word (per_query_dev[q] = the number of hits of q whatever `cap` is; TA_CROSS_UPPER restricts EVERY output
+ * to the pairs with target index > query index; any other flag bit: TA_ERR_ARG).  Every QUERY is at most 256 bytes: a longer bound (the
+ * strided len, the CSR max_len given or measured) is TA_ERR_UNSUPPORTED; targets may have any length below 2^32.  Nothing of size
+ * nq x nt is allocated or written.
+ * TA_ERR_ARG: NULL queries / targets / costs / count_dev; an unknown flag bit; then the costs (TA_ERR_BAD_COSTS, TA_ERR_UNSUPPORTED); then
+ * nq or nt of 2^32 or more; with nq, nt > 0 a NULL blob; cap > 0 with NULL hits_dev; cap * sizeof(ta_cross_hit) overflowing; the length
+ * bounds.  All of these come before any device work.  No device: TA_ERR_HIP.  nq == 0 or nt == 0: TA_OK, the count zero, every nearest
+ * word all ones, every per-query count zero.
+ * The call enqueues its work on `stream` and returns without synchronising; the counter, nearest_dev and per_query_dev are initialised
+ * by kernels.  With every length bound known it is capturable as the two entries above are; a CSR side with max_len = 0 costs one
+ * synchronisation to measure it.  With the longest query at most 64 bytes the kernel is ta_levenshtein_cross's,
+ * lev_cross_kernel<NW, TRANS>; beyond, lev_cross_win_kernel<WW, TRANS>, which keeps a window of WW = 2, 3 or 4 32-row blocks of the
+ * column around the diagonal (k <= 8, 24, 40 in units of the gap cost) or all 8. */
+int ta_levenshtein_cross_with_opts(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt,
+                                   uint32_t k, const ta_edit_costs *costs, uint32_t flags,
+                                   ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                   uint64_t *nearest_dev    /* nq entries, or NULL */,
+                                   uint32_t *per_query_dev  /* nq entries, or NULL */, void *stream);
+
 /* Every needle of a panel searched in every haystack of a batch within k, on device-resident data: the shape a demultiplexer or an
  * adapter trimmer asks for -- 12 adapters, 96 sample barcodes, a primer set against a batch of reads: which needle occurs where in every
  * read (no reference analogue: the reference searches one needle in one haystack per call, src/levenshtein.rs:1911-1966).  The two cross

@@ -413,6 +413,33 @@ def levenshtein_nearest_many(queries, targets, k, costs=LEVENSHTEIN_COSTS):
     return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32) for w in words]
 
 
+def levenshtein_cross_with_opts_many(queries, targets, k, costs=LEVENSHTEIN_COSTS, upper=False):
+    """levenshtein_cross_many for queries of up to 256 bytes (ta_levenshtein_cross_with_opts): the sorted list of (q, t, d) with d =
+    levenshtein_simd_k_with_opts(queries[q], targets[t], k, false, costs) for every pair where that is not None; upper = True keeps only
+    the pairs with t > q (a set against itself: each unordered pair once).  Both lists are uploaded; when there are more hits than the
+    first call's room, one more call runs with room for the count it reported."""
+    from . import batch as B
+    qs, ts = _cross_sides(queries, targets)
+    k = _k(k)
+    hits, count, _, _ = B.levenshtein_cross_with_opts(qs, ts, k, costs, upper=upper)
+    n = int(count.cpu()[0].item())
+    if n > hits.shape[0]:
+        hits, count, _, _ = B.levenshtein_cross_with_opts(qs, ts, k, costs, cap=n, upper=upper)
+    q, t, d = B.cross_to_arrays(hits, count)
+    return [(int(a), int(b), int(c)) for a, b, c in zip(q, t, d)]
+
+
+def levenshtein_nearest_with_opts_many(queries, targets, k, costs=LEVENSHTEIN_COSTS):
+    """For every query of up to 256 bytes its nearest target within k and how many targets are within k, in ONE device call
+    (ta_levenshtein_cross_with_opts, counting only): a list of (target, distance, n_hits) -- the smallest distance, at equal distance
+    the lowest target index -- or None where no target is within k."""
+    from . import batch as B
+    qs, ts = _cross_sides(queries, targets)
+    _, _, nearest, per_query = B.levenshtein_cross_with_opts(qs, ts, _k(k), costs, cap=0, nearest=True, per_query=True)
+    words, counts = nearest.cpu().numpy().view("uint64"), per_query.cpu().numpy().view("uint32")
+    return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32, int(c)) for w, c in zip(words, counts)]
+
+
 def hamming_cross_many(queries, targets, k, upper=False):
     """Every query against every target in ONE device call (ta_hamming_cross): the sorted list of (q, t, d) with d =
     hamming(queries[q], targets[t]) for every pair of equal length where that is at most k; upper = True keeps only the pairs with t > q

@@ -542,6 +542,41 @@ def hamming_cross(queries: Strings, targets: Strings, k, cap=None, hits=None, co
     return hits, count, nearest, per_query
 
 
+def levenshtein_cross_with_opts(queries: Strings, targets: Strings, k, costs=LEVENSHTEIN_COSTS, cap=None, hits=None, count=None, nearest=False,
+                                per_query=False, upper=False):
+    """levenshtein_cross with queries of up to 256 bytes and hamming_cross's two further outputs, on the device
+    (ta_levenshtein_cross_with_opts): -> (hits, count, nearest, per_query).  The hit rule, hits, count, nearest, cap and the costs are
+    levenshtein_cross's; per_query = True (or an int32 tensor of queries.n elements to reuse): per_query[q] = the number of hits of query
+    q, whatever cap is; else None.  upper = True keeps only the pairs with target index > query index, in every output: a set against
+    itself gives each unordered pair once.  A query longer than 256 bytes raises NotImplementedError.  Nothing is synchronised: read
+    count before trusting hits."""
+    nq, nt, dev = queries.n, targets.n, targets.blob.device
+    if cap is None:
+        cap = hits.numel() // 4 if hits is not None else min(nq * nt, max(1024, 8 * max(nq, nt)))
+    hits = torch.empty((cap, 4), dtype=torch.int32, device=dev) if hits is None else hits
+    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+    if nearest is True:
+        nearest = torch.empty(nq, dtype=torch.int64, device=dev)
+    elif nearest is False:
+        nearest = None
+    if per_query is True:
+        per_query = torch.empty(nq, dtype=torch.int32, device=dev)
+    elif per_query is False:
+        per_query = None
+    assert hits.dtype == torch.int32 and hits.is_contiguous() and hits.numel() >= cap * 4
+    assert count.dtype == torch.int64 and count.numel() >= 1
+    assert nearest is None or (nearest.dtype == torch.int64 and nearest.is_contiguous() and nearest.numel() >= nq)
+    assert per_query is None or (per_query.dtype == torch.int32 and per_query.is_contiguous() and per_query.numel() >= nq)
+    cc = _costs(costs)._c()
+    rc = _n.lib().ta_levenshtein_cross_with_opts(queries._ref(), nq, targets._ref(), nt, int(k), _C.byref(cc), _n.TA_CROSS_UPPER if upper else 0,
+                                                 hits.data_ptr() if cap else None, count.data_ptr(), cap,
+                                                 None if nearest is None else nearest.data_ptr(),
+                                                 None if per_query is None else per_query.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return hits, count, nearest, per_query
+
+
 def cross_to_arrays(hits, count, allow_cut=False):
     """the device result of levenshtein_cross as numpy arrays (query, target, k), sorted by (query, target) (host copy).  More hits than
     the `cap` rows of `hits` were cut on the device (count says how many there are): that is an error here, not a silently shorter

@@ -1,6 +1,6 @@
-// ta_cross.hip -- ta_levenshtein_cross, ta_hamming_cross, ta_levenshtein_search_cross and ta_hamming_search_cross
-// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.16): validation, the length bounds, the query tile / the sub-batches and the launches of
-// lev_cross.hip / ham_cross.hip / lev_search_cross.hip / ham_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
+// ta_cross.hip -- ta_levenshtein_cross, ta_levenshtein_cross_with_opts, ta_hamming_cross, ta_levenshtein_search_cross and ta_hamming_search_cross
+// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.17): validation, the length bounds, the query tile / the sub-batches and the launches of
+// lev_cross.hip / lev_cross_win.hip / ham_cross.hip / lev_search_cross.hip / ham_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
 // there is no synchronisation and the call can be captured into a graph.  The shared host rules (cost check and scale, length bounds,
 // measured maxima) and the scratch slots' names (SLOT_CROSS_CTL, SLOT_SX_*) are those of ta_internal.h; the query tile's rule is
 // lev_plan.h's cross_qtile, the sub-batches' lev_search_cross_body.h's sx_plan.
@@ -8,24 +8,28 @@
 #include <stdint.h>
 
 #include "ham_search_cross_body.h"
+#include "lev_cross_win_body.h"
 #include "lev_search_cross_body.h"
 #include "ta_internal.h"
 
 namespace ta {
 
-// the checks both entries share, in their order: counts, pointers and sizes, then the length bounds that are known without measuring
-static int cross_check_args(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt, const ta_cross_hit *hits_dev, size_t cap) {
+// the checks the cross entries share, in their order: counts, pointers and sizes, then the length bounds that are known without measuring
+// (max_query: the entry's limit on a query's length)
+static int cross_check_args(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt, const ta_cross_hit *hits_dev, size_t cap,
+                            uint32_t max_query = 64) {
     if ((uint64_t)nq >> 32 || (uint64_t)nt >> 32) { set_last_error_msg("2^32 or more queries / targets"); return TA_ERR_ARG; }
     if (nq && nt && (!queries->blob || !targets->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
     if (cap && !hits_dev) { set_last_error_msg("cap > 0 with null hits_dev"); return TA_ERR_ARG; }
     if (cap > SIZE_MAX / sizeof(ta_cross_hit)) { set_last_error_msg("cap * sizeof(ta_cross_hit) overflows"); return TA_ERR_ARG; }
-    if (side_bound_known(queries) && side_bound(queries) > 64) { set_last_error_msg("cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
+    if (side_bound_known(queries) && side_bound(queries) > max_query) { set_last_error_msg(max_query > 64 ? "cross: a query longer than 256 bytes" : "cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
     if (side_bound_known(targets) && side_bound(targets) >> 32) { set_last_error_msg("cross: a target of 2^32 bytes or more"); return TA_ERR_UNSUPPORTED; }
     return device_ready() ? TA_OK : TA_ERR_HIP;
 }
 
 // the longest query and target (measure_max_lens: one synchronisation where a CSR side gives no max_len), under the same two limits
-static int cross_max_lens(const ta_strings *qs, uint32_t nq, const ta_strings *ts, uint32_t nt, hipStream_t st, uint64_t *mq, uint64_t *mt) {
+static int cross_max_lens(const ta_strings *qs, uint32_t nq, const ta_strings *ts, uint32_t nt, hipStream_t st, uint64_t *mq, uint64_t *mt,
+                          uint32_t max_query = 64) {
     unsigned long long *dst = nullptr;
     if (!side_bound_known(qs) || !side_bound_known(ts)) {
         Scratch &c = tls_scratch(SLOT_CROSS_CTL);
@@ -33,7 +37,7 @@ static int cross_max_lens(const ta_strings *qs, uint32_t nq, const ta_strings *t
         dst = (unsigned long long *)c.dev;
     }
     if (int rc = measure_max_lens(qs, nq, ts, nt, dst, st, mq, mt)) return rc;
-    if (*mq > 64) { set_last_error_msg("cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
+    if (*mq > max_query) { set_last_error_msg(max_query > 64 ? "cross: a query longer than 256 bytes" : "cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
     if (*mt >> 32) { set_last_error_msg("cross: a target of 2^32 bytes or more"); return TA_ERR_UNSUPPORTED; }
     return TA_OK;
 }
@@ -93,6 +97,42 @@ extern "C" int ta_levenshtein_cross(const ta_strings *queries, size_t nq, const 
     if ((rc = cross_fill64(count_dev, 0u, 1, st))) return rc;
     if (nearest_dev && (rc = cross_fill64((unsigned long long *)nearest_dev, 0xFFFFFFFFu, nq, st))) return rc;
     TA_HIP(lev_cross_launch(P, max_q <= 32 ? 1 : 2, trans, st));
+    return TA_OK;
+}
+
+extern "C" int ta_levenshtein_cross_with_opts(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt,
+                                              uint32_t k, const ta_edit_costs *costs, uint32_t flags,
+                                              ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                              uint64_t *nearest_dev, uint32_t *per_query_dev, void *stream) {
+    if (!queries || !targets || !costs || !count_dev) { set_last_error_msg("null queries / targets / costs / count_dev"); return TA_ERR_ARG; }
+    if (flags & ~TA_CROSS_UPPER) { set_last_error_msg("levenshtein cross: unknown flag bits"); return TA_ERR_ARG; }
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;                                 // EditCosts::new, src/levenshtein.rs:44-52
+    const bool trans = costs->has_transpose != 0;
+    const uint32_t g = costs_scale(costs);                                         // LEVENSHTEIN_COSTS / RDAMERAU_COSTS: 1; g times one: g
+    if (!g) { set_last_error_msg("cross: unit-cost families and their multiples only"); return TA_ERR_UNSUPPORTED; }
+    int rc = cross_check_args(queries, nq, targets, nt, hits_dev, cap, WIN_MAX_QUERY);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard guard(st);
+    // a measured query of more than 256 bytes is refused before any output is written, as ta_levenshtein_cross does it
+    uint64_t max_q = 0, max_t = 0;
+    if (nq && nt && (rc = cross_max_lens(queries, (uint32_t)nq, targets, (uint32_t)nt, st, &max_q, &max_t, WIN_MAX_QUERY))) return rc;
+    if ((rc = cross_fill64(count_dev, 0u, 1, st))) return rc;
+    if (nearest_dev && (rc = cross_fill64((unsigned long long *)nearest_dev, 0xFFFFFFFFu, nq, st))) return rc;
+    if (per_query_dev && nq) TA_HIP(fill_u32_launch(per_query_dev, 0u, (uint32_t)nq, st));
+    if (nq == 0 || nt == 0) return TA_OK;
+
+    CrossParams P = {};
+    P.q = view_of(queries); P.t = view_of(targets);
+    P.nq = (uint32_t)nq; P.nt = (uint32_t)nt;
+    P.k = k / g; P.g = g;
+    P.flags = flags;
+    P.hits = hits_dev; P.cap = cap; P.count = count_dev; P.nearest = (unsigned long long *)nearest_dev; P.per_query = per_query_dev;
+    P.qtile = cross_qtile(nq, nt, CROSS_MIN_QTILE, 1, env_int("TA_CROSS_QTILE"));   // ta_levenshtein_cross's tile
+    // Up to 64 bytes: the whole column in one or two words (3.13).  Beyond: a window of the column, the smallest that holds the band of
+    // P.k (3.17); TA_CROSS_FULL (tuning) takes the whole column instead.
+    if (max_q <= 64) TA_HIP(lev_cross_launch(P, max_q <= 32 ? 1 : 2, trans, st));
+    else TA_HIP(lev_cross_win_launch(P, env_int("TA_CROSS_FULL") ? (int)WIN_NB : win_ww(P.k), trans, st));
     return TA_OK;
 }
 

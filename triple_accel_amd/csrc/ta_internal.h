@@ -359,19 +359,24 @@ struct HamBatchParams {
 // bits: the bit-sliced form (a shared needle of 1..32 bytes, 4 k <= its length); else the register form up to 64 bytes, the memory form beyond
 hipError_t ham_search_batch_launch(const HamBatchParams &P, bool bits, hipStream_t st);
 
-// ta_levenshtein_cross (lev_cross.hip): one lane per target, a wavefront walks a tile of queries
+// ta_levenshtein_cross, ta_levenshtein_cross_with_opts (lev_cross.hip, lev_cross_win.hip): one lane per target, a wavefront walks a
+// tile of queries
 struct CrossParams {
-    StrView q, t;                 // queries (every one at most 32 nw bytes), targets
+    StrView q, t;                 // queries (every one at most 32 nw bytes; the window kernel: 256), targets
     uint32_t nq, nt;
     uint32_t k, g;                // the unit threshold; distances are reported times g (lev_cost_scale)
     uint32_t qtile;               // queries per wavefront: ceil(nq / qtile) <= 65535
+    uint32_t flags;               // TA_CROSS_UPPER: only pairs with target index > query index
     ta_cross_hit *hits;           // device: cap records, or nullptr with cap = 0
     uint64_t cap;
     unsigned long long *count;    // device, pre-zeroed
     unsigned long long *nearest;  // device: nq words preset to all ones, or nullptr
+    uint32_t *per_query;          // device: nq words pre-zeroed, or nullptr
 };
 constexpr uint32_t CROSS_MIN_QTILE = 16;
 hipError_t lev_cross_launch(const CrossParams &P, int nw, bool trans, hipStream_t st);
+// queries of up to 256 bytes: a window of ww = 2, 3, 4 blocks of the column, or all 8 (ww >= win_ww(P.k), lev_cross_win_body.h)
+hipError_t lev_cross_win_launch(const CrossParams &P, int ww, bool trans, hipStream_t st);
 
 // ta_hamming_cross (ham_cross.hip): one lane per target, kept in nw dwords of registers; a wavefront walks a tile of queries, staged
 // through LDS a chunk of 256 / nw at a time
