@@ -9,8 +9,8 @@
 namespace ta {
 
 // One wavefront per block: the nibble tables sit at the start of the block's LDS, address 0 (the body's table addresses are absolute:
-// lane * 4 | nibble << 8 as they stand), and the CU packs as many blocks as its LDS holds -- 11 of 13,824 bytes, three on three of its
-// four SIMDs: the registers are capped for three wavefronts per SIMD.
+// lane * 4 | nibble << 8 as they stand) and are all of it, 8,192 bytes: the strings stay in registers.  The registers, capped for three
+// wavefronts per SIMD, set the occupancy: 12 wavefronts per CU (the LDS would hold 20).
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void lev_bits_tab_kernel(LevParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if (DevTab::lds_address(lds, lds) != 0u) return;         // (never: this kernel has no static LDS in front of the dynamic one)

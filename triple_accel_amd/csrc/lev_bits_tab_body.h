@@ -1,7 +1,9 @@
 // lev_bits_tab_body.h -- the TABLE form of the bit-parallel band kernel's stride-8 LINE form (lev_bits_body.h): the same band of up to 33
-// diagonals, the same line fetch (parked lines, one piece of each string committed per 16 columns, rings of 3 + 2 pieces), the same
+// diagonals, the same line fetch (every 128-byte line of a string requested once and parked in registers), the same
 // 12-operation recurrence, bottom diagonal, zero-step count and way down -- but the match vector PM comes out of two per-pair nibble
 // tables in LDS instead of 32 byte compares and a gather tree.  Levenshtein only (no transposition term), fixed-length batches.
+// The strings never pass through LDS: this form reads them only through the 16 bytes of each that a block of 16 iterations needs, and
+// those are taken from the parked lines register to register (run(), "the LINE fetch").  LDS holds the tables and nothing else.
 //
 // Tables.  Per wavefront TL[16][64] and TH[16][64] dwords, [entry][lane] (8 KB, at the start of the wavefront's LDS): bank = lane for
 // any per-lane entry, so no access conflicts.  The window's 32 rows sit in 32 ring SLOTS: the row that iteration t inserts (string
@@ -13,7 +15,7 @@
 // Sliding.  After column t's lookup the top row leaves and the row iteration t inserts (this column's bottom diagonal, still a byte
 // compare) takes its slot: bit t & 31 is flipped (ds_xor, one data register) in TL[lo(old)], TH[hi(old)], TL[lo(new)], TH[hi(new)];
 // equal nibbles cancel.  `old` is the very dword `new` was 32 iterations ago: the eight dwords of `a` read for the last 32 iterations
-// stay in registers (F, a ring of names: no moves), so the byte that clears a slot is the byte that set it whatever the rings held --
+// stay in registers (F, a ring of names: no moves), so the byte that clears a slot is the byte that set it whatever the fetch delivered --
 // rows above row 1 and below row a_len included, which need no masking here either (lev_bits_body.h, header).
 // Ordering.  A wavefront's LDS operations execute in order and every lane touches only its own column of the tables: lookup t, four
 // flips, lookup t + 1 needs no barrier.  All of them depend on string bytes only, so column t + 1's lookup is issued before column t's
@@ -36,8 +38,7 @@ struct TabNoProbe {
 };
 
 constexpr uint32_t LEV_TAB_TABLE_BYTES = 8192u;                                  // TL at 0, TH at 4096
-constexpr uint32_t LEV_TAB_SLOT_A = 52u, LEV_TAB_SLOT_B = 36u;                   // rings of 3 and 2 pieces + 4 bytes of wrap copy
-constexpr uint32_t LEV_TAB_LDS_PER_WAVE = LEV_TAB_TABLE_BYTES + 64u * (LEV_TAB_SLOT_A + LEV_TAB_SLOT_B);   // 13,824 bytes: 11 wavefronts per CU
+constexpr uint32_t LEV_TAB_LDS_PER_WAVE = LEV_TAB_TABLE_BYTES;                   // the tables and nothing else: LDS leaves room for more wavefronts than the registers do
 
 template <class W, class T, class PROBE = TabNoProbe>
 struct LevBitsTab {
@@ -102,12 +103,13 @@ struct LevBitsTab {
     }
 
     // 16 iterations tb .. tb + 15, tb & 31 == 16 PH; r[g] / bw[g] = the dwords of `a` / `b` of iterations tb + 4 g .. + 3.  TAIL: only the
-    // first `left` (1..16) of them run (the columns end inside the span)
+    // first `left` (1..16) of them run (the columns end inside the span).  Warm-up spans (!COLUMN) leave out their first `skip` (0..16)
+    // iterations: rows in front of the string, which run() has put into the tables already
     template <int PH, bool COLUMN, bool TAIL>
-    static TA_HD inline __attribute__((always_inline)) void span(State &st, uint8_t *lds, const U32 (&r)[4], const U32 (&bw)[4], uint32_t left) {
+    static TA_HD inline __attribute__((always_inline)) void span(State &st, uint8_t *lds, const U32 (&r)[4], const U32 (&bw)[4], uint32_t left, uint32_t skip) {
         if (COLUMN) lookup<0>(st, lds, bw[0]);
 #define TA_TAB_STEP(I)                                                                                                   \
-        if (!TAIL || left > (uint32_t)(I)) {                                                                             \
+        if ((!TAIL || left > (uint32_t)(I)) && (COLUMN || skip <= (uint32_t)(I))) {                                      \
             if (TAIL && left == (uint32_t)(I) + 1u) step<16 * PH + (I), COLUMN, false>(st, lds, r[(I) >> 2], bw[(I) >> 2], bw[((I) + 1) >> 2 & 3]); \
             else step<16 * PH + (I), COLUMN, ((I) < 15)>(st, lds, r[(I) >> 2], bw[(I) >> 2], bw[((I) + 1) >> 2 & 3]);    \
         }
@@ -116,17 +118,22 @@ struct LevBitsTab {
 #undef TA_TAB_STEP
     }
 
+    // r[g] = the four bytes from byte 4 (D + g) + sh of the eight dwords p[0..3], c[0..3] (sh = 0..3, one value per wavefront)
+    template <int D>
+    static TA_HD inline __attribute__((always_inline)) void window(U32 (&r)[4], const U32 (&p)[4], const U32 (&c)[4], const U32 &sh) {
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int i = D + g;
+            r[g] = W::alignbyte_v(i + 1 < 4 ? p[(i + 1) & 3] : c[(i + 1) & 3], i < 4 ? p[i & 3] : c[i & 3], sh);
+        }
+    }
+
     static TA_HD inline void run(const LevParams &P, uint32_t wave_index, uint8_t *lds) {
         const U32 lane = W::lane();
         const U32 slot_idx = lane + wave_index * 64u;
         const Bool valid = slot_idx < P.n;
         const U32 pair = P.subset ? W::load_u32(P.subset, slot_idx, valid, 0u) : slot_idx;
         const Bool active = (lane == lane);
-
-        Ptr aptr, bptr;
-        U32 alen, blen;
-        W::load_str(P.a, pair, valid, aptr, alen);     // rows (a lane without a pair points at the batch's first pair; its bytes go nowhere)
-        W::load_str(P.b, pair, valid, bptr, blen);     // columns
 
         // the batch's band (lev_plan.h): diagonals d = j - i in [-nlo, d_hi]; window bit i <-> diagonal d_hi - i.  One geometry per wavefront.
         const uint32_t alen_u = (uint32_t)P.a.len, blen_u = (uint32_t)P.b.len;
@@ -152,84 +159,121 @@ struct LevBitsTab {
         uint32_t nacc = 0;                                     // columns whose bits (the top nacc of st.acc) are not counted yet, <= 32
         auto flush = [&]() { cnt = W::bcnt(st.acc >> (32u - nacc), cnt); nacc = 0; };      // (nacc >= 1)
 
-        // iteration tp inserts a[tp - ca_s] into the window and, from tp = T0 on, runs column tp - T0 + 1 with b[tp - T0]
+        // iteration tp inserts a[tp - T0 + nlo] into the window and, from tp = T0 on, runs column tp - T0 + 1 with b[tp - T0]
         const uint32_t T0 = P.Tw;                              // a multiple of 64 (lev_plan.h)
-        const int32_t ca_s = (int32_t)T0 - (int32_t)nlo_u;
         const uint32_t iters = T0 + blen_u;
 
-        // ---- the LINE fetch of lev_bits_body.h: every 128-byte line of a string requested once, whole, parked in registers and handed to
-        // LDS piece by piece; string offsets before the string are pieces < 0, delivered as zeros
-        constexpr int32_t RA = 3, RB = 2;
-        const U32 a_slot = lane * LEV_TAB_SLOT_A + LEV_TAB_TABLE_BYTES, b_slot = lane * LEV_TAB_SLOT_B + (LEV_TAB_TABLE_BYTES + 64u * LEV_TAB_SLOT_A);
+        // ---- the LINE fetch of lev_bits_body.h: every 128-byte line of a string requested once, whole, and parked in registers.  The strings
+        // never pass through LDS: a block takes its 16 bytes of each string out of the parked line, a wave-uniform eight-way choice of the
+        // piece.  Pieces in front of a string are zeros; the loads deliver zeros at and past its end
+        Ptr aptr, bptr;
+        U32 alen, blen;
+        W::load_str(P.a, pair, valid, aptr, alen);     // rows (a lane without a pair points at the batch's first pair; its bytes go nowhere)
+        W::load_str(P.b, pair, valid, bptr, blen);     // columns (a fixed-length batch: blen is blen_u in every lane)
         Q SA[8], SB[8];
         auto fetch_a = [&](int32_t m) {
 #pragma unroll
             for (int c = 0; c < 8; c++) {
-                const int32_t off = 128 * m + 16 * c;
-                const Bool ok = (off >= 0 && (uint32_t)off < alen_u) ? active : W::bfalse();
-                SA[c] = W::gload16(W::ptr_add(aptr, W::splat(off >= 0 ? (uint32_t)off : 0u)), ok);
+                const uint32_t off = 128u * (uint32_t)m + 16u * (uint32_t)c;
+                const Bool ok = off < alen_u ? active : W::bfalse();
+                SA[c] = W::gload16(W::ptr_add(aptr, W::splat(off)), ok);
             }
         };
         auto fetch_b = [&](int32_t m) {
 #pragma unroll
             for (int c = 0; c < 8; c++) {
-                const int32_t off = 128 * m + 16 * c;
-                const Bool ok = (off >= 0 && (uint32_t)off < blen_u) ? active : W::bfalse();
-                SB[c] = W::gload16(W::ptr_add(bptr, W::splat(off >= 0 ? (uint32_t)off : 0u)), ok);
+                const uint32_t off = 128u * (uint32_t)m + 16u * (uint32_t)c;
+                const Bool ok = off < blen_u ? active : W::bfalse();
+                SB[c] = W::gload16(W::ptr_add(bptr, W::splat(off)), ok);
             }
         };
-        auto put = [&](const Q (&S)[8], int32_t piece, U32 dst, uint32_t wrap_copy_at) {     // wrap_copy_at: 0 = none
-            switch (piece & 7) {                                   // wave-uniform: one of eight stores
-#define TA_PUT(c) case c: { W::lds_store16(lds, dst, S[c], active); if (wrap_copy_at) W::lds_write32(lds, dst + wrap_copy_at, W::qword(S[c], 0)); } break;
-                TA_PUT(0) TA_PUT(1) TA_PUT(2) TA_PUT(3) TA_PUT(4) TA_PUT(5) TA_PUT(6) TA_PUT(7)
-#undef TA_PUT
+        auto take = [&](const Q (&S)[8], int32_t piece, U32 (&d)[4]) {
+            // (case_tag, LAST in every case: lev_bits_body.h, vput -- eight cases that differ only in the index of S would be sunk into one block
+            // that reads S through a pointer, and S would move to scratch memory)
+            switch (piece & 7) {                                   // wave-uniform: one of eight pieces
+#define TA_TAKE(c) case c: { d[0] = W::qword(S[c], 0); d[1] = W::qword(S[c], 1); d[2] = W::qword(S[c], 2); d[3] = W::qword(S[c], 3); W::template case_tag<c>(); } break;
+                TA_TAKE(0) TA_TAKE(1) TA_TAKE(2) TA_TAKE(3) TA_TAKE(4) TA_TAKE(5) TA_TAKE(6) TA_TAKE(7)
+#undef TA_TAKE
             }
         };
-        auto fmod = [](int32_t x, int32_t m) -> uint32_t { const int32_t r = x % m; return (uint32_t)(r < 0 ? r + m : r); };
-        auto commit_a = [&](int32_t piece) {
-            const uint32_t slot = fmod(piece, RA);
-            put(SA, piece, a_slot + 16u * slot, slot == 0u ? 16u * RA : 0u);
-            if ((piece & 7) == 7) fetch_a((piece >> 3) + 1);
+        // The next line's burst is issued when a line's last piece has been taken: 16 iterations ahead of its first piece.  ONE take per
+        // string and block, each in front of the block's branches (take_b serves the warm-up blocks too, with zeros): with a second call
+        // site, or with the take inside a branch, hipcc keeps a second set of 32 registers for the line and copies one onto the other in
+        // every block (64 v_mov per block and string, and scratch at the cap of 168 registers).
+        auto take_a = [&](int32_t piece, U32 (&d)[4]) {
+            if (piece < 0) {
+                d[0] = d[1] = d[2] = d[3] = W::splat(0);
+            } else {
+                take(SA, piece, d);
+                if ((piece & 7) == 7) fetch_a((piece >> 3) + 1);
+            }
         };
-        auto commit_b = [&](int32_t piece) {
-            const uint32_t slot = fmod(piece, RB);
-            put(SB, piece, b_slot + 16u * slot, slot == 0u ? 16u * RB : 0u);
-            if ((piece & 7) == 7) fetch_b((piece >> 3) + 1);
+        auto take_b = [&](int32_t piece, U32 (&d)[4]) {
+            if (piece < 0) {
+                d[0] = d[1] = d[2] = d[3] = W::splat(0);
+            } else {
+                take(SB, piece, d);
+                if ((piece & 7) == 7) fetch_b((piece >> 3) + 1);
+            }
         };
+
+        // Block tb reads a[16 pa + ao ..+15] (pa = (tb - T0) / 16 + nlo / 16, ao = nlo & 15: one number per launch) and b[tb - T0 ..+15], piece
+        // (tb - T0) / 16 exactly.  ao == 0 (cfg2: nlo = 16): the block is piece pa as it stands.  Otherwise it straddles pieces pa and pa + 1:
+        // wa keeps piece pa from the block before, the block takes piece pa + 1 and reads its dwords out of the eight.
+        const uint32_t tb0 = T0 - 32u;
+        const uint32_t ao = nlo_u & 15u;
+        const U32 ash = W::splat(ao & 3u);
+        int32_t pa = (int32_t)(nlo_u >> 4) - 2;
+        U32 wa[4];
+        fetch_a(0);
+        fetch_b(0);
+        if (ao) take_a(pa, wa);
+        else wa[0] = wa[1] = wa[2] = wa[3] = W::splat(0);
 
         // the warm-up: the tables zeroed (eight 16-byte stores per lane cover the 8 KB), then the 32 iterations in front of the first column
-        // insert the first window's rows -- whatever bytes the ring holds for them (zeros above row 1)
+        // insert the first window's rows.  The first npre = 32 - nlo of them lie in front of the string: zero bytes in slots 0 .. npre - 1,
+        // all of them bits of TL[0] and TH[0].  Those go in as one mask and their iterations are skipped (F stays zero for them).
 #pragma unroll
         for (uint32_t i = 0; i < 8u; i++) W::lds_store16(lds, (lane << 4) + 1024u * i, W::qzero(), active);
-        const uint32_t tb0 = T0 - 32u;
-        int32_t qa = ((int32_t)tb0 - ca_s) >> 4, qb = ((int32_t)tb0 - (int32_t)T0) >> 4;
-        fetch_a(qa >> 3);
-        fetch_b(qb >> 3);
-        for (int32_t x = qa; x < qa + RA - 1; x++) commit_a(x);
-        for (int32_t x = qb; x < qb + RB - 1; x++) commit_b(x);
+        W::lds_wave_sync();                                    // (a lane's stores zero four lanes' entries)
+        const uint32_t npre = 32u - (nlo_u < 32u ? nlo_u : 32u);
+        if (npre) {
+            const U32 pre = W::splat(npre >= 32u ? 0xFFFFFFFFu : ((1u << npre) - 1u));
+            W::lds_write32(lds, lane << 2, pre);
+            W::lds_write32(lds, (lane << 2) + 4096u, pre);
+        }
 
-        // one block: a piece of each string into the slot of the piece the last block finished, then its 16 iterations
+        // one block: its dwords of `a` out of the parked line, then its 16 iterations
         auto block = [&](uint32_t tb, auto phase_tag) {
             constexpr int PH = decltype(phase_tag)::value;
-            commit_a(qa + RA - 1);
-            commit_b(qb + RB - 1);
-            qa++; qb++;
-            W::lds_wave_sync();
             U32 r[4], bw[4];
+            U32 w1[4];
+            take_a(pa + (ao ? 1 : 0), w1);
+            if (ao == 0u) {
 #pragma unroll
-            for (uint32_t g = 0; g < 4u; g++) {
-                r[g] = W::lds_read32u(lds, a_slot + fmod((int32_t)(tb + 4u * g) - ca_s, 16 * RA));
-                bw[g] = W::lds_read32u(lds, b_slot + fmod((int32_t)(tb + 4u * g) - (int32_t)T0, 16 * RB));
+                for (int g = 0; g < 4; g++) r[g] = w1[g];
+            } else {
+                switch (ao >> 2) {                             // wave-uniform: the dword the block starts in, then a byte shift
+                    case 0: window<0>(r, wa, w1, ash); break;
+                    case 1: window<1>(r, wa, w1, ash); break;
+                    case 2: window<2>(r, wa, w1, ash); break;
+                    default: window<3>(r, wa, w1, ash); break;
+                }
+#pragma unroll
+                for (int g = 0; g < 4; g++) wa[g] = w1[g];
             }
+            pa++;
+            take_b(((int32_t)tb - (int32_t)T0) >> 4, bw);
             if (tb < T0) {
-                span<PH, false, false>(st, lds, r, bw, 16u);
+                const uint32_t done = tb - tb0;
+                span<PH, false, false>(st, lds, r, bw, 16u, npre > done ? npre - done : 0u);
             } else {
                 PROBE::block(lds, st.F, tb);
                 if (tb + 16u <= iters) {
-                    span<PH, true, false>(st, lds, r, bw, 16u);
+                    span<PH, true, false>(st, lds, r, bw, 16u, 0u);
                     nacc += 16u;
                 } else {
-                    span<PH, true, true>(st, lds, r, bw, iters - tb);
+                    span<PH, true, true>(st, lds, r, bw, iters - tb, 0u);
                     nacc += iters - tb;
                 }
                 if (PH == 1 || tb + 16u >= iters) flush();
@@ -244,7 +288,7 @@ struct LevBitsTab {
         // the way down from the top diagonal's cell to row a_len: idx_ans steps over the last column's vertical differences
         const uint32_t mb = idx_ans >= 32u ? 0xFFFFFFFFu : ((1u << idx_ans) - 1u);
         const U32 tail = W::bcnt(st.VP & mb, W::splat(0)) - W::bcnt(st.VN & mb, W::splat(0));
-        const U32 d = (W::splat(dhi_u) + blen) - cnt + tail;   // the top diagonal starts at d_hi; + columns - zero-difference steps + way down
+        const U32 d = W::splat(dhi_u + blen_u) - cnt + tail;   // the top diagonal starts at d_hi; + columns - zero-difference steps + way down
         const Bool some = (d <= P.k) & (W::splat(inband ? 1u : 0u) != 0u);        // :539-541
         W::store_u32(P.out, pair, W::sel(some, d, W::splat(0xFFFFFFFFu)), valid);
     }
