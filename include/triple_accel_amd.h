@@ -135,7 +135,8 @@ int ta_last_launch_info(ta_launch_info *out);
 
 /* ---- single-call host API (the reference's function set) ------------------------------- */
 
-/* hamming(a, b), src/hamming.rs:390 -> :317 -> :36-47 */
+/* hamming(a, b), src/hamming.rs:390 -> :317 -> :36-47.  A pair of more than 64 MiB per string is staged through the device 64 MiB at
+ * a time (the device holds two such pieces whatever the pair's length); a pair of 64 KiB or more is sliced over the chip. */
 int ta_hamming(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t *out);
 
 /* levenshtein_simd_k_with_opts(a, b, k, trace_on, costs), src/levenshtein.rs:714-720.
@@ -543,8 +544,18 @@ int ta_levenshtein_trace_batch_tokens(const ta_tokens *a, const ta_tokens *b, si
 int ta_levenshtein_tokens(const uint32_t *a, size_t a_len, const uint32_t *b, size_t b_len, uint32_t k,
                           const ta_edit_costs *costs, uint32_t *out, ta_edit **edits, size_t *n_edits);
 
-/* N x hamming(a_i, b_i); out[i] = TA_NONE where the lengths differ (Rust: panic). */
+/* N x hamming(a_i, b_i); out[i] = TA_NONE where the lengths differ (Rust: panic).  Strings below 64 KiB run one wavefront (or a part of
+ * one) per pair; longer ones are cut into slices of 16 KiB, one wavefront per slice, the slices of the whole batch spread over the chip
+ * (strided: len >= 64 KiB; CSR: the same on the sides' max_len, or up to 8,192 pairs without one; never CSR batches of more than 65,536
+ * pairs).  The answers are the same either way and out_dev[i] is stored exactly once.  The sliced form keeps thread-local scratch:
+ * capturable under the rule above. */
 int ta_hamming_batch(const ta_strings *a, const ta_strings *b, size_t n, uint32_t *out_dev, void *stream);
+/* hamming(a, b), src/hamming.rs:390 -> :317, of ONE pair that already lies in device memory as two pointers of `len` bytes each, at any
+ * and different byte alignments: *out_dev = the number of differing positions.  No read slack is needed: nothing outside
+ * [a_dev, a_dev + len) and [b_dev, b_dev + len) is read.  Asynchronous on `stream`, capturable under the rule above; from 64 KiB on
+ * the pair is sliced over the chip (below, one wavefront is faster: the rule is ta_hamming_batch's for one pair).  len = 0: *out_dev = 0 (the pointers may be NULL).  A NULL out_dev, or a NULL string with
+ * len > 0: TA_ERR_ARG.  len >= 0xFFFFFFFF: TA_ERR_UNSUPPORTED (the count is a u32 and 0xFFFFFFFF is TA_NONE). */
+int ta_hamming_dev(const uint8_t *a_dev, const uint8_t *b_dev, size_t len, uint32_t *out_dev, void *stream);
 
 /* ---- a queue for callers that produce pairs ONE AT A TIME (the reference's calling convention, src/levenshtein.rs:714-720) but
  * can wait for the answers: a single call costs a kernel launch (22-25 us for a 256-byte pair, against ~2 us on a host core);

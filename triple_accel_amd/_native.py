@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "ta_levenshtein_cross", "ta_hamming_cross", "ta_levenshtein_cross_with_opts",
     # every needle of a panel in every haystack (ta_cross.hip)
     "ta_levenshtein_search_cross", "ta_hamming_search_cross",
+    # hamming of one long pair resident in HBM (ham_long.hip)
+    "ta_hamming_dev",
 ]
 
 TA_CROSS_UPPER = 1          # ta_hamming_cross flags: only pairs with target index > query index
@@ -164,6 +166,7 @@ def lib():
     sig("ta_levenshtein_trace_batch", i32, [sp, sp, sz, u32, cp, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     sig("ta_levenshtein_trace_batch_packed", i32, [sp, sp, sz, u32, cp, C.c_void_p, C.c_void_p, C.c_void_p, sz, C.c_void_p])
     sig("ta_hamming_batch", i32, [sp, sp, sz, C.c_void_p, C.c_void_p])
+    sig("ta_hamming_dev", i32, [C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p])
     sig("ta_levenshtein_search_dev", i32, [u8p, sz, C.c_void_p, sz, u32, cp, i32, C.c_uint64, C.c_uint64,
                                            C.c_void_p, sz, C.POINTER(C.c_uint64), C.c_void_p])
     sig("ta_hamming_search_dev", i32, [u8p, sz, C.c_void_p, sz, u32, C.c_uint64, C.c_void_p, sz,

@@ -306,6 +306,22 @@ def hamming_batch(a: Strings, b: Strings, out=None):
     return out
 
 
+def hamming_dev(a, b, out=None):
+    """hamming(a, b) (src/hamming.rs:390) of ONE pair that lies in HBM (ta_hamming_dev): two 1-D contiguous torch.uint8 CUDA tensors of
+    the same length -- views at any storage offset are fine, no read slack is needed -- -> a 1-element device tensor.  From 64 KiB on the
+    pair is cut into slices spread over the whole chip.  Asynchronous on the current stream; capturable after one call outside the capture."""
+    for t in (a, b):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.dim() == 1 and t.is_contiguous()):
+            raise ValueError("hamming_dev: 1-D contiguous torch.uint8 CUDA tensors")
+    if a.numel() != b.numel():
+        _raise(_n.TA_ERR_LEN_MISMATCH)                          # assert!(a.len() == b.len()), src/hamming.rs:318
+    out = _out(1, a.device) if out is None else out
+    rc = _n.lib().ta_hamming_dev(a.data_ptr() if a.numel() else None, b.data_ptr() if b.numel() else None, a.numel(), out.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return out
+
+
 # ---------------------------------------------------------------- search on a haystack shard resident in HBM
 def _hits_to_numpy(hits_t, count):
     """(start, end, k) rows sorted by end.  An end position is reported at most once per call, so `end` alone orders

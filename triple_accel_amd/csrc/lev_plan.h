@@ -34,6 +34,51 @@ static inline bool lev_is_unit(uint32_t mc, uint32_t gc, uint32_t sg, bool has_t
 }
 // ragged (CSR) batches of this size take their pairs in length order (util_kernels.hip: length_order_launch)
 static inline bool lev_wants_length_order(bool any_csr, uint64_t n, uint64_t max_len) { return any_csr && n >= 4096 && max_len >= 16; }
+// ---- hamming of long strings (ham_long.hip): a pair cut into slices of HAM_LONG_SLICE bytes, one wavefront per slice, a
+// grid of at most HAM_LONG_GRID_WAVES wavefronts striding over the slice ids.
+constexpr uint32_t HAM_LONG_SLICE = 16384;          // bytes per slice (a multiple of 1,024); TA_HAM_SLICE under TA_TUNING
+constexpr uint32_t HAM_LONG_GRID_WAVES = 8192;      // two resident sets of wavefronts (256 CUs x 4 SIMDs x 4); TA_HAM_GRID under TA_TUNING
+constexpr uint32_t HAM_LONG_MAX_SLICES = 1u << 20;  // the slice length doubles until a batch of `bytes` bytes has at most this many full slices
+constexpr uint32_t HAM_CSR_MAX_PAIRS = 65536;       // CSR batches beyond fill the chip by count and keep one wavefront per pair
+// The routing constants, from the measured crossover of the two routes (scripts/measure_hamming_long.py, rows "crossover" of
+// profiles/r11/measure_hamming_long.jsonl; old = hamming_batch_kernel, new = this form; ms per call, strided batches resident in HBM):
+//     pairs      32 KiB: old / new      64 KiB: old / new      128 KiB: old / new
+//         1      0.0074 / 0.0093        0.0133 / 0.0092        0.0246 / 0.0094
+//        64      0.0077 / 0.0095        0.0133 / 0.0095        0.0246 / 0.0097
+//     1,024      0.0139 / 0.0167        0.0267 / 0.0259        0.0553 / 0.0442
+//     8,192      0.0931 / 0.0939        0.1884 / 0.1827        0.3831 / 0.3679
+// The sliced form is two launches (three for CSR: the plan) and never ran under 0.009 ms; one wavefront of the old kernel walks 32 KiB in
+// 0.0074 ms.  Below 64 KiB the old kernel won at EVERY pair count measured (512 bytes .. 32 KiB: old / new = 0.56 .. 0.99); from 64 KiB
+// on the sliced form won at every one -- by 1.4 x for up to 64 pairs, by a few per cent from 1,024 pairs on, where the old kernel's
+// wavefronts already fill the chip (2,000 x 64 KiB is a tie: 0.92 .. 1.02 over three sessions).  The design started with a second clause
+// -- "longer than one trip per lane (1 KiB) and fewer pairs than two resident sets" -- which the measurement did not bear out at any
+// pair count; it is gone, the rule is one length.
+constexpr uint64_t HAM_SLICE_MIN_LEN = 65536;       // strings of at least this many bytes: sliced whatever the pair count
+constexpr uint64_t HAM_SLICE_NOHINT_PAIRS = 8192;   // a CSR batch WITHOUT a length hint is sliced up to this many pairs: its lengths are unknown, the
+                                                    // sliced form costs at most 0.005 ms more (above), the old one a whole pair per wavefront
+#if defined(__HIPCC__)
+#define TA_PLAN_HD __host__ __device__
+#else
+#define TA_PLAN_HD
+#endif
+// the slice length a batch of `bytes` bytes in all runs with: s0, doubled (up to 256 MiB) while bytes / S exceeds HAM_LONG_MAX_SLICES
+static inline TA_PLAN_HD uint32_t ham_long_slice_bytes(uint64_t bytes, uint32_t s0) {
+    uint32_t s = s0;
+    while (bytes / s > HAM_LONG_MAX_SLICES && s < (1u << 28)) s <<= 1;
+    return s;
+}
+// Does ta_hamming_batch take the sliced form?  Host-known values only: n pairs; strided = both sides in the strided form with the same
+// `len`; a CSR batch's max_len_hint = the smallest length bound a side states (0: none).
+static inline bool ham_wants_slices(uint64_t n, bool strided, uint64_t len, uint64_t max_len_hint) {
+    if (n == 0 || n > 0xFFFFFFFFull) return false;
+    if (!strided) {
+        if (n > HAM_CSR_MAX_PAIRS) return false;
+        if (!max_len_hint) return n <= HAM_SLICE_NOHINT_PAIRS;
+        len = max_len_hint;
+    }
+    return len >= HAM_SLICE_MIN_LEN;
+}
+
 // Queries per wavefront of the cross entries (ta_cross.hip): about 16,384 wavefronts (8 per SIMD of 256 CUs, twice over), at least
 // min_tile, whole multiples of round_to, at most 512, `forced` (> 0: a tuning switch) as it is, and never more than 65,535 tiles (the
 // grid's y dimension).  Levenshtein: (CROSS_MIN_QTILE, 1); Hamming: (0, its staging chunk).

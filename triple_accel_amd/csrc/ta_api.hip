@@ -751,13 +751,69 @@ int ta_levenshtein_exp_batch(const ta_strings *a, const ta_strings *b, size_t n,
     return TA_OK;
 }
 
+// The sliced form of hamming (ham_long.hip).  ham_wants_slices (lev_plan.h) is the rule; under TA_TUNING,
+// TA_FORCE_HAM_SLICED=1 / =0 pin the route and TA_HAM_SLICE=<bytes> (a multiple of 1,024, at least 1,024) sets the slice length.
+}  // extern "C"
+namespace ta {
+uint32_t ham_slice_setting() {
+    const int v = env_int("TA_HAM_SLICE");
+    return v >= 1024 && v % 1024 == 0 && v <= (1 << 28) ? (uint32_t)v : HAM_LONG_SLICE;
+}
+// the smallest length bound the two sides state for a pair of EQUAL lengths (the others are TA_NONE whatever their lengths); 0: none
+static uint64_t ham_len_hint(const ta_strings *a, const ta_strings *b) {
+    const uint64_t ha = side_bound_known(a) ? side_bound(a) : 0, hb = side_bound_known(b) ? side_bound(b) : 0;
+    return ha && hb ? (ha < hb ? ha : hb) : (ha ? ha : hb);
+}
+static bool ham_route_sliced(const ta_strings *a, const ta_strings *b, size_t n) {
+    const bool strided = !a->off && !b->off;
+    if (strided && a->len != b->len) return false;          // every answer is TA_NONE: nothing to slice
+    bool sliced = ham_wants_slices(n, strided, a->len, strided ? 0 : ham_len_hint(a, b));
+    if (const char *f = env_str("TA_FORCE_HAM_SLICED")) sliced = atoi(f) != 0;
+    return sliced;
+}
+// the sliced pass over a device batch: plan (CSR), slices, finish -- out_dev[i] is stored exactly once, by the finish kernel
+static int ham_long_pass(const StrView &a, const StrView &b, uint32_t n, uint32_t *out_dev, hipStream_t st, bool *taken) {
+    const uint32_t S = ham_slice_setting();
+    const uint64_t words = ham_long_scratch_words(a, b, n, S);
+    *taken = words != 0;
+    if (!words) return TA_OK;                                // more than 2^31 slices: the batch fills the chip by count
+    Scratch &sc = tls_scratch(SLOT_HAM_LONG);
+    int rc = sc.ensure(words * 4u);
+    if (rc) return rc;
+    TA_HIP(ham_long_launch(a, b, n, S, (uint32_t *)sc.dev, out_dev, st));
+    return TA_OK;
+}
+}  // namespace ta
+extern "C" {
+
 int ta_hamming_batch(const ta_strings *a, const ta_strings *b, size_t n, uint32_t *out_dev, void *stream) {
     int rc = check_batch_args(a, b, n, out_dev);
     if (rc) return rc;
     if (!device_ready()) return TA_ERR_HIP;
     if (n == 0) return TA_OK;
     StreamGuard guard((hipStream_t)stream);
+    if (ham_route_sliced(a, b, n)) {
+        bool taken = false;
+        if ((rc = ham_long_pass(view_of(a), view_of(b), (uint32_t)n, out_dev, (hipStream_t)stream, &taken))) return rc;
+        if (taken) return TA_OK;
+    }
     TA_HIP(hamming_batch_launch(view_of(a), view_of(b), (uint32_t)n, out_dev, (hipStream_t)stream));
+    return TA_OK;
+}
+
+int ta_hamming_dev(const uint8_t *a_dev, const uint8_t *b_dev, size_t len, uint32_t *out_dev, void *stream) {
+    if (!out_dev || (len && (!a_dev || !b_dev))) return TA_ERR_ARG;
+    if (len >= 0xFFFFFFFFull) return TA_ERR_UNSUPPORTED;     // the count is a u32 and 0xFFFFFFFF is TA_NONE
+    if (!device_ready()) return TA_ERR_HIP;
+    StreamGuard guard((hipStream_t)stream);
+    const StrView va = {a_dev, nullptr, 0, len}, vb = {b_dev, nullptr, 0, len};
+    bool sliced = ham_wants_slices(1, true, len, 0);         // ta_hamming_batch's rule for one strided pair
+    if (const char *f = env_str("TA_FORCE_HAM_SLICED")) sliced = atoi(f) != 0;
+    if (sliced) {
+        bool taken = false;
+        return ham_long_pass(va, vb, 1, out_dev, (hipStream_t)stream, &taken);      // (one pair of < 4 GiB: always taken)
+    }
+    TA_HIP(hamming_batch_launch(va, vb, 1, out_dev, (hipStream_t)stream));           // one wavefront; it too reads nothing past len
     return TA_OK;
 }
 
@@ -936,19 +992,54 @@ int fetch_u32(const Staged &S, uint32_t *out, bool single_store /* = false */) {
     return TA_OK;
 }
 
+// hamming of a host pair longer than `chunk` bytes: the pair goes through two fixed device halves (one per string) chunk by chunk on the
+// thread's stream -- copy, copy, sliced kernel with its partial counts appended -- and one finish kernel adds them up at the end.  The
+// stream alone orders the steps (a chunk's copies wait for the kernel that read the halves before).  The device holds 2 x chunk bytes
+// whatever the pair's length (stage_pair would hold the whole pair).
+static int hamming_host_chunked(const uint8_t *a, const uint8_t *b, size_t len, size_t chunk, uint32_t *out) {
+    if (!a || !b || len > 0xFFFFFFF0ull) return TA_ERR_ARG;
+    if (!device_ready()) return TA_ERR_HIP;
+    CallCtx &cx = call_ctx();
+    int rc = cx.ensure();
+    if (rc) return rc;
+    StreamGuard guard(cx.st);
+    const uint32_t S = ham_long_slice_bytes(len, ham_slice_setting());
+    const size_t half = (chunk + 255) & ~(size_t)255, n_chunks = (len + chunk - 1) / chunk;
+    Scratch &stage = tls_scratch(SLOT_PAIR_STAGE), &part = tls_scratch(SLOT_HAM_LONG);
+    if ((rc = stage.ensure(2 * half + 256))) return rc;
+    if ((rc = part.ensure((len / S + n_chunks + 1) * 4u))) return rc;
+    uint8_t *da = (uint8_t *)stage.dev, *db = da + half;
+    uint32_t *out_dev = (uint32_t *)(db + half), *partial = (uint32_t *)part.dev;
+    uint32_t done = 0;
+    for (size_t at = 0; at < len; at += chunk) {
+        const size_t m = len - at < chunk ? len - at : chunk;
+        TA_HIP(hipMemcpyAsync(da, a + at, m, hipMemcpyHostToDevice, cx.st));
+        TA_HIP(hipMemcpyAsync(db, b + at, m, hipMemcpyHostToDevice, cx.st));
+        TA_HIP(ham_long_chunk_launch(da, db, m, S, partial + done, cx.st));
+        done += (uint32_t)((m + S - 1) / S);
+    }
+    TA_HIP(ham_long_sum_launch(partial, done, out_dev, cx.st));
+    TA_HIP(hipMemcpyAsync(out, out_dev, 4, hipMemcpyDeviceToHost, cx.st));
+    TA_HIP(hipStreamSynchronize(cx.st));
+    return TA_OK;
+}
 }  // namespace ta
-
 extern "C" {
 
 int ta_hamming(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len, uint32_t *out) {
     if (!out) return TA_ERR_ARG;
     if (a_len != b_len) return TA_ERR_LEN_MISMATCH;          // src/hamming.rs:318
+    size_t chunk = HAM_HOST_CHUNK;                           // bytes of each string on the device at a time; TA_HAM_HOST_CHUNK under TA_TUNING
+    if (const int v = env_int("TA_HAM_HOST_CHUNK"); v >= 1024) chunk = (size_t)v;
+    if (a_len > chunk) return hamming_host_chunked(a, b, a_len, chunk, out);
     Staged S;
     int rc = stage_pair(a, a_len, b, b_len, &S);
     if (rc) return rc;
     rc = ta_hamming_batch(&S.sa, &S.sb, 1, S.out_dev, S.st);
     if (rc) return rc;
-    return fetch_u32(S, out, true);                          // one kernel, one store
+    // either route stores the slot exactly once: the one kernel of hamming_batch_kernel, or the finish kernel of the sliced form (its
+    // partial counts live in scratch, never in the slot) -- the pinned word can be watched
+    return fetch_u32(S, out, true);
 }
 
 int ta_levenshtein_simd_k_with_opts(const uint8_t *a, size_t a_len, const uint8_t *b, size_t b_len,

@@ -92,6 +92,8 @@ enum ScratchSlot {
     SLOT_HSX_CTL = 34,       // ta_hamming_search_cross: measure_max_lens' two 64-bit words ...
     SLOT_HSX_WORD = 35,      // ... and the packed nearest words (d << 48 | needle << 32 | start), one per haystack, live from the fill to the
                              // finish kernel.  34, 35: that entry alone.
+    SLOT_HAM_LONG = 36,      // ham_long.hip: the plan of a CSR batch and the per-slice counts, dead once the finish kernel has run (ta_hamming_batch,
+                             // ta_hamming_dev, the chunked ta_hamming).  Alone.
     TA_SCRATCH_SLOTS
 };
 Scratch &tls_scratch(ScratchSlot which);
@@ -232,6 +234,14 @@ hipError_t lev_wide_u32_launch(const LevParams &P, bool trans, bool trace, hipSt
 struct SymCompactParams;
 hipError_t sym_compact_launch(const SymCompactParams &P, uint32_t waves, hipStream_t s);
 hipError_t hamming_batch_launch(const StrView &a, const StrView &b, uint32_t n, uint32_t *out, hipStream_t s);
+// hamming of long strings (ham_long.hip): every pair cut into slices, one wavefront per slice; scratch = ham_long_scratch_words() u32
+// (0: the batch has more than 2^31 slices and stays on hamming_batch_kernel).  The chunk / sum pair serves a host pair that is staged piece by piece.
+uint64_t ham_long_scratch_words(const StrView &a, const StrView &b, uint32_t n, uint32_t S0);
+hipError_t ham_long_launch(const StrView &a, const StrView &b, uint32_t n, uint32_t S0, uint32_t *scratch, uint32_t *out, hipStream_t st);
+hipError_t ham_long_chunk_launch(const uint8_t *a, const uint8_t *b, uint64_t len, uint32_t S, uint32_t *partial, hipStream_t st);
+hipError_t ham_long_sum_launch(const uint32_t *partial, uint32_t n_partial, uint32_t *out, hipStream_t st);
+uint32_t ham_slice_setting();      // HAM_LONG_SLICE, or TA_HAM_SLICE under TA_TUNING
+constexpr size_t HAM_HOST_CHUNK = 64ull << 20;     // ta_hamming: bytes of each host string on the device at a time
 hipError_t strings_maxlen_launch(const StrView &s, uint32_t n, uint32_t *out_max /*device, pre-zeroed*/, hipStream_t st);
 hipError_t compact_none_launch(const uint32_t *out, const uint32_t *subset_in, uint32_t n_in, const uint32_t *n_in_dev /*optional: the list's length on the device*/,
                                uint32_t *subset_out, uint32_t *count, hipStream_t st);
