@@ -9,9 +9,11 @@
 namespace ta {
 
 // One wavefront per block: the nibble tables sit at the start of the block's LDS, address 0 (the body's table addresses are absolute:
-// lane * 4 | nibble << 8 as they stand) and are all of it, 8,192 bytes: the strings stay in registers.  The registers, capped for three
-// wavefronts per SIMD, set the occupancy: 12 wavefronts per CU (the LDS would hold 20).
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void lev_bits_tab_kernel(LevParams P) {
+// lane * 4 | nibble << 8 as they stand) and are all of it, 8,192 bytes: the strings stay in registers.  The registers, capped for four
+// wavefronts per SIMD (128; the kernel takes 125, no scratch), set the occupancy: 16 wavefronts per CU = 128 KB of the CU's 160 KB of LDS
+// (the LDS would hold 20).  The body holds no slot-bit constants across the column loop (lev_bits_tab_body.h, step()): parked, they were
+// 32 registers more and the cap was three wavefronts per SIMD.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void lev_bits_tab_kernel(LevParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     if (DevTab::lds_address(lds, lds) != 0u) return;         // (never: this kernel has no static LDS in front of the dynamic one)
     LevBitsTab<DevWave, DevTab>::run(P, blockIdx.x, lds);
@@ -22,11 +24,15 @@ hipError_t lev_bits_tab_launch(const LevParams &P0, hipStream_t s, uint32_t *gri
     P.lds_per_wave = LEV_TAB_LDS_PER_WAVE;
     const uint32_t waves = (P.n + 63u) / 64u;
     const uint32_t grid = waves;
+    // TA_TAB_LDS_PAD_KB (TA_TUNING only, the occupancy probe of profiles/r12): unused KB behind the tables, so that fewer wavefronts share
+    // a CU -- 16 / 14 / 13 / 12 of them at 0 / 3 / 4 / 5.  The kernel never touches the pad
+    const int pad_kb = env_int("TA_TAB_LDS_PAD_KB");
+    const uint32_t lds = LEV_TAB_LDS_PER_WAVE + 1024u * (uint32_t)(pad_kb < 0 ? 0 : pad_kb > 56 ? 56 : pad_kb);
     if (grid_out) *grid_out = grid;
-    if (lds_out) *lds_out = LEV_TAB_LDS_PER_WAVE;
+    if (lds_out) *lds_out = lds;
     set_last_kernel_name("lev_bits_tab_kernel");
     if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(lev_bits_tab_kernel, dim3(grid), dim3(64), LEV_TAB_LDS_PER_WAVE, s, P);
+    hipLaunchKernelGGL(lev_bits_tab_kernel, dim3(grid), dim3(64), lds, s, P);
     return hipGetLastError();
 }
 

@@ -67,11 +67,14 @@ struct LevBitsTab {
 
     // iteration t with t & 31 == S: byte S & 3 of a_new enters slot S (COLUMN: byte S & 3 of F[S >> 2] leaves it), then column t - T0 + 1 runs on
     // the lookup issued a step ago.  NEXT: issue the next column's lookup (byte (S + 1) & 3 of b_next) behind this iteration's flips.
+    // The slot bit is made HERE, opaque to the compiler: the flips take their data from a VGPR, and left as a plain constant all 32 of them
+    // are hoisted in front of the column loop and parked for the life of the wavefront -- 32 registers and the fourth wavefront per SIMD
+    // (157 against 125 VGPRs) for one v_mov_b32 per column.
     template <int S, bool COLUMN, bool NEXT>
     static TA_HD inline __attribute__((always_inline)) void step(State &st, uint8_t *lds, const U32 &a_new, const U32 &b_dw, const U32 &b_next) {
         constexpr int C = S & 3;
         const U32 mL = st.mL, mH = st.mH;
-        const U32 bit = W::splat(1u << S);
+        const U32 bit = W::opaque(W::splat(1u << S));
         if (COLUMN) {
             T::template nib_to_byte1<C>(st.aOL, st.aOH, st.F[S >> 2]);
             T::lds_abs_xor32(lds, st.aOL, bit);

@@ -242,8 +242,9 @@ static inline LevBits2Plan lev_bits2_make_plan(uint32_t k, uint32_t mc, uint32_t
 // ---- table form of the stride-8 line form (lev_bits_tab_body.h): the match vector from two per-pair nibble tables in LDS.  Its domain is
 // the stride-8 LINE form's Levenshtein case -- no transposition term, a fixed-length batch in the line form of the fetch (strings longer
 // than one 128-byte line), no checkpoints, no early out, a pair count the host knows; costs that are multiples of the unit costs arrive
-// here as unit costs (lev_unit_scale).  The route takes it from LEV_BITS_TAB_MIN_PAIRS pairs on: its registers leave 12 wavefronts per CU
-// (8 KB of tables each) instead of 16, which a launch has to be big enough to fill anyway.
+// here as unit costs (lev_unit_scale).  The route takes it from LEV_BITS_TAB_MIN_PAIRS pairs on: one resident set of its 16 wavefronts per CU
+// (8 KB of tables each).  Forced, it has been the faster form from 125,000 pairs on in every sweep so far (profiles/r08, r10, r12); no
+// smaller batch was measured, so the threshold stands.
 constexpr uint32_t LEV_BITS_TAB_MIN_PAIRS = 262144;
 static inline bool lev_bits_tab_in_domain(const LevBitsPlan &pl, bool has_t, bool line_form, uint64_t max_len) {
     return pl.ok && pl.s8 && !has_t && line_form && max_len > 128u && (pl.Tw & 63u) == 0u;
