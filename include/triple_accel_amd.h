@@ -214,6 +214,8 @@ void ta_free(void *p);
  * device-mapped buffer of that thread -- one kernel launch and one stream synchronisation per call.  The batch / *_dev
  * functions run on the stream the caller passes; a thread that switches streams between two such calls is ordered by an
  * event the library records at the end of each call (the thread-local scratch of the first call may still be in use).
+ * The single-call functions are ordered after the thread's earlier batch / *_dev calls in the same way: their stream waits for
+ * that event before it touches the scratch they share with them (tests/test_gpu_stream_order.py holds every entry to this).
  * ta_thread_release() frees what the calling thread holds inside the library (device scratch, its stream, the pinned
  * buffer); optional -- without it they live until process exit.
  * Graph capture.  The batch / *_dev entries that say so may be captured into a hipGraph (hipStreamBeginCapture on the stream they are given).

@@ -279,6 +279,7 @@ int ta_levenshtein_tokens(const uint32_t *a, size_t a_len, const uint32_t *b, si
     int rc = call_ctx().ensure();
     if (rc) return rc;
     hipStream_t st = call_ctx().st;
+    StreamGuard guard(st);                                                      // (SLOT_TRACE and SLOT_LINES are the batch entries' too)
     if (!edits) return wide_pair_u32(a, a_len, b, b_len, k, costs, st, out, nullptr);
     std::optional<ScriptBuilder<uint32_t>> res;
     if ((rc = wide_pair_u32(a, a_len, b, b_len, k, costs, st, out, &res))) return rc;

@@ -280,6 +280,12 @@ int ta_levenshtein_trace(const uint8_t *a, size_t a_len, const uint8_t *b, size_
     const bool swap = a_len > b_len;                                            // :386-390
     const uint8_t *x = swap ? b : a, *y = swap ? a : b;
     const size_t n = swap ? b_len : a_len, m = swap ? a_len : b_len;
+    // every route below keeps its records in thread-local scratch that the batch entries share (SLOT_LINES, SLOT_TRACE) and runs on the
+    // thread's own stream: ordered after the thread's earlier calls on other streams like any batch call (StreamGuard, ta_internal.h)
+    CallCtx &cx = call_ctx();
+    int rc = cx.ensure();
+    if (rc) return rc;
+    StreamGuard guard(cx.st);
     ta_lev_select sel;
     ta_levenshtein_select(n, m, k, costs, &sel);
     const uint32_t gc = costs->gap_cost, sg = costs->start_gap_cost;
@@ -299,8 +305,7 @@ int ta_levenshtein_trace(const uint8_t *a, size_t a_len, const uint8_t *b, size_
         return trace_wide(x, n, y, m, swap, k, costs, out, edits, n_edits, code_words, tcols);
     }
     Staged S;
-    int rc = stage_pair(x, n, y, m, &S);
-    if (rc) return rc;
+    if ((rc = stage_pair(x, n, y, m, &S))) return rc;
     const uint32_t tw = (uint32_t)lev_trace_words(pl.D);
     const size_t taus = (n + m + 1) / 2 + 1;
     const size_t trace_words = taus * 2 * 64 * tw;
