@@ -10,8 +10,8 @@ namespace ta {
 
 // One wavefront per block: the nibble tables sit at the start of the block's LDS, address 0 (the body's table addresses are absolute:
 // lane * 4 | nibble << 8 as they stand) and are all of it, 8,192 bytes: the strings stay in registers.  The registers, capped for four
-// wavefronts per SIMD (128; the kernel takes 125, no scratch), set the occupancy: 16 wavefronts per CU = 128 KB of the CU's 160 KB of LDS
-// (the LDS would hold 20).  The body holds no slot-bit constants across the column loop (lev_bits_tab_body.h, step()): parked, they were
+// wavefronts per SIMD (128; the kernel takes 121, no scratch), set the occupancy: 16 wavefronts per CU = 128 KB of the CU's 160 KB of LDS
+// (the LDS would hold 20).  The body holds no slot-bit constants across the column loop (lev_bits_tab_body.h, flips()): parked, they were
 // 32 registers more and the cap was three wavefronts per SIMD.
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void lev_bits_tab_kernel(LevParams P) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
@@ -30,6 +30,8 @@ hipError_t lev_bits_tab_launch(const LevParams &P0, hipStream_t s, uint32_t *gri
     const uint32_t lds = LEV_TAB_LDS_PER_WAVE + 1024u * (uint32_t)(pad_kb < 0 ? 0 : pad_kb > 56 ? 56 : pad_kb);
     if (grid_out) *grid_out = grid;
     if (lds_out) *lds_out = lds;
+    // TA_TAB_DEPTH (TA_TUNING only): the depth that does not ship, from lev_bits_tab_alt.hip; any other value is the default's
+    if (env_int("TA_TAB_DEPTH") == LEV_TAB_ALT_DEPTH) return lev_bits_tab_alt_launch(P, grid, lds, s);
     set_last_kernel_name("lev_bits_tab_kernel");
     if (grid == 0) return hipSuccess;
     hipLaunchKernelGGL(lev_bits_tab_kernel, dim3(grid), dim3(64), lds, s, P);

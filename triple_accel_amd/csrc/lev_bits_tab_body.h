@@ -19,7 +19,13 @@
 // rows above row 1 and below row a_len included, which need no masking here either (lev_bits_body.h, header).
 // Ordering.  A wavefront's LDS operations execute in order and every lane touches only its own column of the tables: lookup t, four
 // flips, lookup t + 1 needs no barrier.  All of them depend on string bytes only, so column t + 1's lookup is issued before column t's
-// recurrence and its latency sits under VALU work.
+// recurrence and its latency sits under VALU work -- which the compiler has to be held to: left alone, hipcc lifts the next column's
+// `mL & mH` into the current recurrence and every column waits for the whole queue, lgkmcnt(0), a third of a column behind its lookup.
+// column() PINS the point where a lookup is consumed (W::opaque on the two table words), span() puts the next column's flips, its lookup
+// and the addresses of the column after in front of that point, and the wait becomes a counted one that leaves those operations
+// outstanding: lgkmcnt(6).  DEPTH = the lookups in flight inside a span: 1 ships; 2 issues flips t + 1 and lookup t + 2 in front of
+// column t (lgkmcnt(12)) and measured slower (profiles/r13/ab_band_tab_waits.md).  tests/test_lev_bits_tab_waits_cpu.py reads the waits
+// out of the assembly.
 // Addresses.  lane * 4 | nibble << 8 (+ 4096 as the instruction's offset for TH): ONE SDWA instruction per address writes the nibble of the selected
 // byte into byte 1 of a register that holds lane * 4 (T::nib_to_byte1, both addresses of a byte in one call; T = the table form's own operations, wave_tab.h).  They are ABSOLUTE LDS addresses
 // (T::lds_abs_read32 / lds_abs_xor32): `lds` must be the start of the block's LDS, address 0 -- one wavefront per block, no static LDS.
@@ -40,8 +46,14 @@ struct TabNoProbe {
 constexpr uint32_t LEV_TAB_TABLE_BYTES = 8192u;                                  // TL at 0, TH at 4096
 constexpr uint32_t LEV_TAB_LDS_PER_WAVE = LEV_TAB_TABLE_BYTES;                   // the tables and nothing else: LDS leaves room for more wavefronts than the registers do
 
-template <class W, class T, class PROBE = TabNoProbe>
+// how far the LDS stream runs ahead of the recurrence inside a span (span(), "Ordering" above): the depth the kernel ships with.  The other
+// one is lev_bits_tab_alt.hip's (TA_TAB_DEPTH under TA_TUNING)
+constexpr int LEV_TAB_DEPTH = 1;
+constexpr int LEV_TAB_ALT_DEPTH = 3 - LEV_TAB_DEPTH;
+
+template <class W, class T, class PROBE = TabNoProbe, int DEPTH = LEV_TAB_DEPTH>
 struct LevBitsTab {
+    static_assert(DEPTH == 1 || DEPTH == 2, "one or two lookups in flight");
     using U32 = typename W::U32;
     using Bool = typename W::Bool;
     using Ptr = typename W::Ptr;
@@ -54,71 +66,114 @@ struct LevBitsTab {
         U32 F[8];               // the dwords of `a` of the last 32 iterations: dword (t >> 2) & 7 holds iteration t's byte in byte t & 3
         U32 aLL, aLH;           // table addresses (byte 0 = lane * 4, byte 1 = the nibble): the lookup's,
         U32 aOL, aOH, aNL, aNH; // the leaving row's and the entering row's
-        U32 mL, mH;             // the lookup in flight: TL[b & 15], TH[b >> 4] of the next column
+        U32 bit;
+        U32 mL[DEPTH + 1], mH[DEPTH + 1];   // the lookups: TL[b & 15], TH[b >> 4] of column J (of its span) in [J % (DEPTH + 1)] -- DEPTH in flight and the one its column runs on
     };
 
-    // table entries of the column character, byte C of b_dw
-    template <int C>
-    static TA_HD inline __attribute__((always_inline)) void lookup(State &st, const uint8_t *lds, const U32 &b_dw) {
-        T::template nib_to_byte1<C>(st.aLL, st.aLH, b_dw);
-        st.mL = T::lds_abs_read32(lds, st.aLL);
-        st.mH = T::lds_abs_read32(lds, st.aLH + 4096u);
+    // the addresses of column J's table entries (byte J & 3 of b_dw), then the two reads
+    template <int J>
+    static TA_HD inline __attribute__((always_inline)) void lookup_addr(State &st, const U32 &b_dw) {
+        T::template nib_to_byte1<J & 3>(st.aLL, st.aLH, b_dw);
+    }
+    template <int J>
+    static TA_HD inline __attribute__((always_inline)) void lookup_read(State &st, const uint8_t *lds) {
+        st.mL[J % (DEPTH + 1)] = T::lds_abs_read32(lds, st.aLL);
+        st.mH[J % (DEPTH + 1)] = T::lds_abs_read32(lds, st.aLH + 4096u);
     }
 
-    // iteration t with t & 31 == S: byte S & 3 of a_new enters slot S (COLUMN: byte S & 3 of F[S >> 2] leaves it), then column t - T0 + 1 runs on
-    // the lookup issued a step ago.  NEXT: issue the next column's lookup (byte (S + 1) & 3 of b_next) behind this iteration's flips.
+    // Iteration t with t & 31 == S in three parts, so that a span can order them (span()).
+    // flip_addr: the addresses of the four flips -- byte S & 3 of a_new enters slot S, and (COLUMN) byte S & 3 of F[S >> 2] leaves it.
+    template <int S, bool COLUMN>
+    static TA_HD inline __attribute__((always_inline)) void flip_addr(State &st, const U32 &a_new) {
+        if (COLUMN) T::template nib_to_byte1<S & 3>(st.aOL, st.aOH, st.F[S >> 2]);
+        T::template nib_to_byte1<S & 3>(st.aNL, st.aNH, a_new);
+    }
+    // flips: the four of them, and a_new takes its place in F behind its last byte.
     // The slot bit is made HERE, opaque to the compiler: the flips take their data from a VGPR, and left as a plain constant all 32 of them
     // are hoisted in front of the column loop and parked for the life of the wavefront -- 32 registers and the fourth wavefront per SIMD
     // (157 against 125 VGPRs) for one v_mov_b32 per column.
-    template <int S, bool COLUMN, bool NEXT>
-    static TA_HD inline __attribute__((always_inline)) void step(State &st, uint8_t *lds, const U32 &a_new, const U32 &b_dw, const U32 &b_next) {
-        constexpr int C = S & 3;
-        const U32 mL = st.mL, mH = st.mH;
-        const U32 bit = W::opaque(W::splat(1u << S));
+    template <int S, bool COLUMN, bool OWN_BIT>
+    static TA_HD inline __attribute__((always_inline)) void flips(State &st, uint8_t *lds, const U32 &a_new) {
+        const U32 bit = OWN_BIT ? W::opaque(W::splat(1u << S)) : st.bit;
         if (COLUMN) {
-            T::template nib_to_byte1<C>(st.aOL, st.aOH, st.F[S >> 2]);
             T::lds_abs_xor32(lds, st.aOL, bit);
             T::lds_abs_xor32(lds, st.aOH + 4096u, bit);
         }
-        T::template nib_to_byte1<C>(st.aNL, st.aNH, a_new);
         T::lds_abs_xor32(lds, st.aNL, bit);
         T::lds_abs_xor32(lds, st.aNH + 4096u, bit);
-        if (COLUMN && NEXT) lookup<(S + 1) & 3>(st, lds, b_next);
-        if (COLUMN) {
-            const U32 m = mL & mH;
-            U32 PM;
-            if constexpr (S == 0) PM = m; else PM = W::template alignbit<(S ? S : 1)>(m, m);
-            // the recurrence of lev_bits_body.h, step8 (no transposition term), operation by operation
-            const U32 pv = PM & st.VP;
-            U32 sum;
-            const typename W::Mask cm = W::add_carry_mask(pv, st.VP, sum);
-            const U32 X = bitop3<0xBE>(sum, st.VP, PM);                 // (sum ^ VP) | PM
-            const U32 D0 = X | st.VN;
-            const U32 d0_bot = W::template byte_eq_or<C>(a_new, b_dw, cm);   // the 33rd diagonal: match | carry, in bit 0
-            const U32 HP = bitop3<0xF1>(st.VN, X, st.VP);               // VN | ~(X | VP)
-            const U32 HN = X & st.VP;
-            st.acc = W::template alignbit<1>(D0, st.acc);
-            const U32 D0s = W::template alignbit<1>(d0_bot, D0);
-            st.VP = bitop3<0xF1>(HN, D0s, HP);                          // HN | ~(D0s | HP)
-            st.VN = D0s & HP;
-        }
-        if (C == 3) st.F[S >> 2] = a_new;
+        if ((S & 3) == 3) st.F[S >> 2] = a_new;
+    }
+    // column: column t - T0 + 1 on its lookup, which was issued DEPTH steps ago.  THE PIN: the two table words pass through W::opaque right
+    // here, so the lookup is consumed at this point of the instruction stream and no earlier -- behind the issue of everything span() puts
+    // in front of this call, and the wait that hipcc puts here is a counted one that leaves those operations outstanding.  Without the pin
+    // the scheduler lifts `mL & mH` into the middle of the column before and waits there for the whole queue, lgkmcnt(0), in every column.
+    template <int S>
+    static TA_HD inline __attribute__((always_inline)) void column(State &st, const U32 &a_new, const U32 &b_dw) {
+        constexpr int C = S & 3;
+        const U32 mH = W::opaque(st.mH[(S & 15) % (DEPTH + 1)]);        // (the later of the two reads first: one wait serves both)
+        const U32 mL = W::opaque(st.mL[(S & 15) % (DEPTH + 1)]);
+        if constexpr ((S & 15) + DEPTH < 16) st.bit = W::opaque(W::splat(1u << (S + DEPTH)));
+        const U32 m = mL & mH;
+        U32 PM;
+        if constexpr (S == 0) PM = m; else PM = W::template alignbit<(S ? S : 1)>(m, m);
+        // the recurrence of lev_bits_body.h, step8 (no transposition term), operation by operation
+        const U32 pv = PM & st.VP;
+        U32 sum;
+        const typename W::Mask cm = W::add_carry_mask(pv, st.VP, sum);
+        const U32 X = bitop3<0xBE>(sum, st.VP, PM);                 // (sum ^ VP) | PM
+        const U32 D0 = X | st.VN;
+        const U32 d0_bot = W::template byte_eq_or<C>(a_new, b_dw, cm);   // the 33rd diagonal: match | carry, in bit 0
+        const U32 HP = bitop3<0xF1>(st.VN, X, st.VP);               // VN | ~(X | VP)
+        const U32 HN = X & st.VP;
+        st.acc = W::template alignbit<1>(D0, st.acc);
+        const U32 D0s = W::template alignbit<1>(d0_bot, D0);
+        st.VP = bitop3<0xF1>(HN, D0s, HP);                          // HN | ~(D0s | HP)
+        st.VN = D0s & HP;
     }
 
     // 16 iterations tb .. tb + 15, tb & 31 == 16 PH; r[g] / bw[g] = the dwords of `a` / `b` of iterations tb + 4 g .. + 3.  TAIL: only the
-    // first `left` (1..16) of them run (the columns end inside the span).  Warm-up spans (!COLUMN) leave out their first `skip` (0..16)
-    // iterations: rows in front of the string, which run() has put into the tables already
+    // first `left` (1..16) of them run (the columns end inside the span); nothing is issued for the others.  Warm-up spans (!COLUMN) leave
+    // out their first `skip` (0..16) iterations: rows in front of the string, which run() has put into the tables already.
+    // A column span finds lookup 0 issued (block()).  Its LDS stream is lookup 0, flips 0, lookup 1, flips 1, ... whatever the depth; the
+    // depth says where the recurrences stand in it.  Step I issues flips I + DEPTH - 1 and lookup I + DEPTH, makes the addresses of the
+    // step after, and then runs column I: at depth 1 on a lookup that has had one column's time and waits with 6 operations outstanding,
+    // at depth 2 two columns' and 12.  The lead is built in front of step 0 and runs out in the last DEPTH steps: at the span's end every
+    // flip below tb + 16 is issued and nothing beyond.
     template <int PH, bool COLUMN, bool TAIL>
     static TA_HD inline __attribute__((always_inline)) void span(State &st, uint8_t *lds, const U32 (&r)[4], const U32 (&bw)[4], uint32_t left, uint32_t skip) {
-        if (COLUMN) lookup<0>(st, lds, bw[0]);
+        if constexpr (!COLUMN) {
+#define TA_TAB_WARM(I)                                                                                                   \
+            if (skip <= (uint32_t)(I)) { flip_addr<16 * PH + (I), false>(st, r[(I) >> 2]); flips<16 * PH + (I), false, true>(st, lds, r[(I) >> 2]); }
+            TA_TAB_WARM(0) TA_TAB_WARM(1) TA_TAB_WARM(2) TA_TAB_WARM(3) TA_TAB_WARM(4) TA_TAB_WARM(5) TA_TAB_WARM(6) TA_TAB_WARM(7)
+            TA_TAB_WARM(8) TA_TAB_WARM(9) TA_TAB_WARM(10) TA_TAB_WARM(11) TA_TAB_WARM(12) TA_TAB_WARM(13) TA_TAB_WARM(14) TA_TAB_WARM(15)
+#undef TA_TAB_WARM
+        } else {
+            // iteration J's LDS operations, J = 0..15 (nothing for J >= left in a tail): the four flips and column J + 1's lookup; then
+            // the addresses of iteration J + 1's
+#define TA_TAB_ADDR(J)                                                                                                   \
+            if ((J) < 16) {                                                                                              \
+                flip_addr<16 * PH + ((J) & 15), true>(st, r[((J) & 15) >> 2]);                                           \
+                if ((J) + 1 < 16) lookup_addr<((J) + 1) & 15>(st, bw[(((J) + 1) & 15) >> 2]);                            \
+            }
+#define TA_TAB_ISSUE(J)                                                                                                  \
+            if ((J) < 16 && (!TAIL || left > (uint32_t)(J))) {                                                           \
+                flips<16 * PH + ((J) & 15), true, ((J) < DEPTH)>(st, lds, r[((J) & 15) >> 2]);                                          \
+                if ((J) + 1 < 16 && (!TAIL || left > (uint32_t)(J) + 1u)) lookup_read<((J) + 1) & 15>(st, lds);          \
+                TA_TAB_ADDR((J) + 1)                                                                                     \
+            }
 #define TA_TAB_STEP(I)                                                                                                   \
-        if ((!TAIL || left > (uint32_t)(I)) && (COLUMN || skip <= (uint32_t)(I))) {                                      \
-            if (TAIL && left == (uint32_t)(I) + 1u) step<16 * PH + (I), COLUMN, false>(st, lds, r[(I) >> 2], bw[(I) >> 2], bw[((I) + 1) >> 2 & 3]); \
-            else step<16 * PH + (I), COLUMN, ((I) < 15)>(st, lds, r[(I) >> 2], bw[(I) >> 2], bw[((I) + 1) >> 2 & 3]);    \
-        }
-        TA_TAB_STEP(0) TA_TAB_STEP(1) TA_TAB_STEP(2) TA_TAB_STEP(3) TA_TAB_STEP(4) TA_TAB_STEP(5) TA_TAB_STEP(6) TA_TAB_STEP(7)
-        TA_TAB_STEP(8) TA_TAB_STEP(9) TA_TAB_STEP(10) TA_TAB_STEP(11) TA_TAB_STEP(12) TA_TAB_STEP(13) TA_TAB_STEP(14) TA_TAB_STEP(15)
+            if (!TAIL || left > (uint32_t)(I)) {                                                                         \
+                TA_TAB_ISSUE((I) + DEPTH - 1)                                                                            \
+                column<16 * PH + (I)>(st, r[(I) >> 2], bw[(I) >> 2]);                                                    \
+            }
+            TA_TAB_ADDR(0)
+            if constexpr (DEPTH == 2) { TA_TAB_ISSUE(0) }
+            TA_TAB_STEP(0) TA_TAB_STEP(1) TA_TAB_STEP(2) TA_TAB_STEP(3) TA_TAB_STEP(4) TA_TAB_STEP(5) TA_TAB_STEP(6) TA_TAB_STEP(7)
+            TA_TAB_STEP(8) TA_TAB_STEP(9) TA_TAB_STEP(10) TA_TAB_STEP(11) TA_TAB_STEP(12) TA_TAB_STEP(13) TA_TAB_STEP(14) TA_TAB_STEP(15)
 #undef TA_TAB_STEP
+#undef TA_TAB_ISSUE
+#undef TA_TAB_ADDR
+        }
     }
 
     // r[g] = the four bytes from byte 4 (D + g) + sh of the eight dwords p[0..3], c[0..3] (sh = 0..3, one value per wavefront)
@@ -154,7 +209,8 @@ struct LevBitsTab {
             st.VP = W::splat(~below);
         }
         st.acc = W::splat(0);
-        st.mL = W::splat(0); st.mH = W::splat(0);
+#pragma unroll
+        for (int i = 0; i <= DEPTH; i++) st.mL[i] = st.mH[i] = W::splat(0);
 #pragma unroll
         for (int i = 0; i < 8; i++) st.F[i] = W::splat(0);
         st.aLL = st.aLH = st.aOL = st.aOH = st.aNL = st.aNH = lane << 2;
@@ -251,6 +307,11 @@ struct LevBitsTab {
             constexpr int PH = decltype(phase_tag)::value;
             U32 r[4], bw[4];
             U32 w1[4];
+            // column 0's lookup first: it needs bw[0] and the flips of the block before, which are issued, and nothing else -- the choice
+            // of the block's dwords of `a` runs under it.  Unconditional, like the takes: a warm-up block looks up TL[0] / TH[0] for nobody.
+            take_b(((int32_t)tb - (int32_t)T0) >> 4, bw);
+            lookup_addr<0>(st, bw[0]);
+            lookup_read<0>(st, lds);
             take_a(pa + (ao ? 1 : 0), w1);
             if (ao == 0u) {
 #pragma unroll
@@ -266,7 +327,6 @@ struct LevBitsTab {
                 for (int g = 0; g < 4; g++) wa[g] = w1[g];
             }
             pa++;
-            take_b(((int32_t)tb - (int32_t)T0) >> 4, bw);
             if (tb < T0) {
                 const uint32_t done = tb - tb0;
                 span<PH, false, false>(st, lds, r, bw, 16u, npre > done ? npre - done : 0u);

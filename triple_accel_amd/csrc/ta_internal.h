@@ -212,6 +212,8 @@ hipError_t lev_bits_launch(const LevParams &P, const LevBitsPlan &pl, bool trans
                            uint32_t *grid_out, uint32_t *lds_out);
 // the table form of the stride-8 line form (lev_bits_tab.hip): what lev_bits_launch hands the batches tab_form_wanted() names
 hipError_t lev_bits_tab_launch(const LevParams &P, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out);
+// the same at the depth that does not ship (lev_bits_tab_alt.hip): lev_bits_tab_launch's, under TA_TUNING with TA_TAB_DEPTH
+hipError_t lev_bits_tab_alt_launch(const LevParams &P, uint32_t grid, uint32_t lds, hipStream_t s);
 // the VLINE fetch form (lev_bits_vline.hip): CSR batches through the stride-8 window
 hipError_t lev_bits_vline_launch(const LevParams &P, const LevBitsPlan &pl, bool trans, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out);
 hipError_t lev_bitsq_launch(const LevParams &P, bool trans, hipStream_t s, uint32_t *grid_out, uint32_t *lds_out);

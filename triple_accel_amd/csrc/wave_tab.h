@@ -16,25 +16,26 @@ struct DevTab {
     // other three bytes of both stay -> TWO SDWA instructions (v_and_b32 / v_lshrrev_b32 on the selected byte, written to byte 1 with the
     // rest of the destination preserved).  hipcc's own sequence is v_bfe_u32 + v_lshl_or_b32 and a copy of the base, per address.
     // On gfx940 and later a VALU instruction that reads a register in the slot right behind a sub-dword write to it needs one wait state,
-    // which the compiler does not count across asm statements.  Both writes are ONE statement: the second instruction (which reads neither
-    // result) is the first one's wait state, and the s_nop 0 that ends the statement is the second one's, whatever the compiler puts
-    // behind it (a copy, a spill, the add of a base).  The two registers must be different ones.  (s_nop is not a VALU instruction, but it
-    // takes an issue slot: one per pair measured 1.1 % on cfg2, one per address 3 %.)
+    // Both writes are ONE statement: the second instruction (which reads neither result) is the first one's wait state.  The second
+    // one's is the compiler's to keep: hipcc takes every VGPR an asm statement writes for such a write and puts an s_nop in front of a VALU
+    // instruction or another statement that reads it in the next slot (it did so in every such place while the body was being ordered).
+    // The body has no such reader: an address goes to LDS instructions, which are not VALU instructions, and to the next statement on the
+    // same register a column later.  A statement used to end in an s_nop 0 of its own -- three issue slots per column, 0.6 % of cfg2
+    // (profiles/r13) -- and tests/test_lev_bits_tab_waits_cpu.py now reads the kernels' assembly for a VALU reader in the slot behind.
+    // The two registers must be different ones.
+    // VOLATILE: the statements keep their order among themselves and against W::opaque, which is how the body places a column's addresses
+    // in front of its wait (lev_bits_tab_body.h, column()).
     template <int N>
     static __device__ __forceinline__ void nib_to_byte1(U32 &addr_lo, U32 &addr_hi, U32 x) {
         static_assert(N >= 0 && N < 4, "byte index");
-        if constexpr (N == 0) asm("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_0\n\t"
-                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_0\n\t"
-                                  "s_nop 0" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
-        if constexpr (N == 1) asm("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_1\n\t"
-                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_1\n\t"
-                                  "s_nop 0" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
-        if constexpr (N == 2) asm("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_2\n\t"
-                                  "s_nop 0" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
-        if constexpr (N == 3) asm("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_3\n\t"
-                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_3\n\t"
-                                  "s_nop 0" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
+        if constexpr (N == 0) asm volatile("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_0\n\t"
+                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_0" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
+        if constexpr (N == 1) asm volatile("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_1\n\t"
+                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_1" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
+        if constexpr (N == 2) asm volatile("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_2\n\t"
+                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_2" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
+        if constexpr (N == 3) asm volatile("v_and_b32_sdwa %0, 15, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_3\n\t"
+                                  "v_lshrrev_b32_sdwa %1, 4, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:BYTE_3" : "+v"(addr_lo), "+v"(addr_hi) : "v"(x));
     }
     // LDS by ABSOLUTE address (one wavefront per block and no static LDS, so the block's LDS starts at address 0 and `addr` is the
     // instruction's address operand as it stands -- through `lds + off` hipcc adds the base, a link-time zero, with a VALU instruction per
