@@ -466,6 +466,28 @@ int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn, const ta_s
                                 ta_match *best_dev         /* nh entries, or NULL */,
                                 uint32_t *per_haystack_dev /* nh entries, or NULL */, void *stream);
 
+/* ta_levenshtein_search_cross for panels with needles of up to 64 bytes: read-through adapters (33, 34 bytes), full-length indexed
+ * adapters, primer-plus-tag constructs (the reference searches one needle in one haystack per call, src/levenshtein.rs:1911-1966; R(p, i)
+ * is the same list: the end == 0 match :1693-1706, the empty-needle answers :1919-1963, the overlap fold :1812-1835).  The contract is
+ * ta_levenshtein_search_cross's word for word -- records, count, cap, nearest_dev, best_dev, per_haystack_dev, both string forms, empty
+ * sides, asynchrony, capture, bounded scratch -- with two differences:
+ *   1. every NEEDLE is at most 64 bytes: a longer bound (the strided len, the CSR max_len given or measured) is TA_ERR_UNSUPPORTED;
+ *   2. `flags` must be 0: any set bit is TA_ERR_ARG (the word is reserved), checked behind the NULL pointers and before the costs.
+ * The error order is otherwise the same: NULL pointers, flags, costs, blobs / cap / overflow, the limits, TA_ERR_HIP.
+ * Routes, decided once per call from the panel's longest-needle bound.  Up to 32 bytes: exactly the kernels, the sub-batch plan and the
+ * ta_last_kernel_name of ta_levenshtein_search_cross.  33..64 bytes: the two-word route for the WHOLE panel -- the scan
+ * on two dwords per needle against 32 needles per half wavefront, lev_search_cross_w2_scan_kernel<TRANS>, then the exact recurrence with
+ * its column in device scratch (at most 256 MB of columns), lev_search_cross_w2_exact_kernel<TRANS>, which ta_last_kernel_name names when the
+ * call is anchored.  The word count is not chosen per group of needles (a CSR panel's lengths are known on the device only), so short
+ * needles in a long panel pay for two words and for the memory-backed column: a caller with 96 barcodes and 2 long adapters does better
+ * with two calls, one per entry. */
+int ta_levenshtein_search_cross_with_opts(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                          uint32_t k, const ta_edit_costs *costs, int anchored, uint32_t flags,
+                                          ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                          uint64_t *nearest_dev      /* nh entries, or NULL */,
+                                          ta_match *best_dev         /* nh entries, or NULL */,
+                                          uint32_t *per_haystack_dev /* nh entries, or NULL */, void *stream);
+
 /* Every needle of a panel searched in every haystack of a batch within k MISMATCHES, on device-resident data: the Hamming twin of
  * ta_levenshtein_search_cross, for panels designed around a minimum Hamming distance -- sample barcodes behind staggers, inline indices,
  * primers -- where "at most k mismatches, no indels" is the rule (at k = 1 the Levenshtein entry also accepts a shifted tag, and its

@@ -467,20 +467,33 @@ def hamming_nearest_many(queries, targets, k):
     return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32, int(c)) for w, c in zip(words, counts)]
 
 
+def _search_cross_many(entry, needles, haystacks, k, costs, anchored):
+    from . import batch as B
+    nd, hs = _cross_sides(needles, haystacks)
+    k = _k(k)
+    hits, count, *_ = entry(nd, hs, k, costs, anchored)
+    n = int(count.cpu()[0].item())
+    if n > hits.shape[0]:
+        hits, count, *_ = entry(nd, hs, k, costs, anchored, cap=n)
+    cols = B.search_cross_to_arrays(hits, count)
+    return [(int(i), int(p), Match(int(s), int(e), int(d)), int(m)) for i, p, s, e, d, m in zip(*cols)]
+
+
+def _search_nearest_many(entry, needles, haystacks, k, costs, anchored):
+    nd, hs = _cross_sides(needles, haystacks)
+    _, _, nearest, best, per = entry(nd, hs, _k(k), costs, anchored, cap=0, nearest=True, best=True, per_haystack=True)
+    words, rows, counts = nearest.cpu().numpy().view("uint64"), best.cpu().numpy(), per.cpu().numpy().view("uint32")
+    return [(None, None, 0) if int(w) == 0xFFFFFFFFFFFFFFFF else
+            (int(w) & 0xFFFFFFFF, Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF), int(c)) for w, r, c in zip(words, rows, counts)]
+
+
 def levenshtein_search_cross_many(needles, haystacks, k, costs=LEVENSHTEIN_COSTS, anchored=False):
     """Every needle searched in every haystack in ONE device call (ta_levenshtein_search_cross): the sorted list of (haystack, needle,
     Match, n_matches) for every pair where R = levenshtein_search_simd_with_opts(needles[p], haystacks[i], k, SearchType.Best, costs,
     anchored) is not empty, with Match = R[0] and n_matches = len(R).  Needles of at most 32 bytes.  Both lists are uploaded; when there
     are more hits than the first call's room, one more call runs with room for the count it reported."""
     from . import batch as B
-    nd, hs = _cross_sides(needles, haystacks)
-    k = _k(k)
-    hits, count, *_ = B.levenshtein_search_cross(nd, hs, k, costs, anchored)
-    n = int(count.cpu()[0].item())
-    if n > hits.shape[0]:
-        hits, count, *_ = B.levenshtein_search_cross(nd, hs, k, costs, anchored, cap=n)
-    cols = B.search_cross_to_arrays(hits, count)
-    return [(int(i), int(p), Match(int(s), int(e), int(d)), int(m)) for i, p, s, e, d, m in zip(*cols)]
+    return _search_cross_many(B.levenshtein_search_cross, needles, haystacks, k, costs, anchored)
 
 
 def levenshtein_search_nearest_many(needles, haystacks, k, costs=LEVENSHTEIN_COSTS, anchored=False):
@@ -488,11 +501,19 @@ def levenshtein_search_nearest_many(needles, haystacks, k, costs=LEVENSHTEIN_COS
     (ta_levenshtein_search_cross, counting only): a list of (needle index | None, Match | None, needles that hit) -- the smallest
     R[0].k, at equal cost the lowest needle index.  needles that hit == 1 is the demultiplexer's "exactly one barcode within k"."""
     from . import batch as B
-    nd, hs = _cross_sides(needles, haystacks)
-    _, _, nearest, best, per = B.levenshtein_search_cross(nd, hs, _k(k), costs, anchored, cap=0, nearest=True, best=True, per_haystack=True)
-    words, rows, counts = nearest.cpu().numpy().view("uint64"), best.cpu().numpy(), per.cpu().numpy().view("uint32")
-    return [(None, None, 0) if int(w) == 0xFFFFFFFFFFFFFFFF else
-            (int(w) & 0xFFFFFFFF, Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF), int(c)) for w, r, c in zip(words, rows, counts)]
+    return _search_nearest_many(B.levenshtein_search_cross, needles, haystacks, k, costs, anchored)
+
+
+def levenshtein_search_cross_with_opts_many(needles, haystacks, k, costs=LEVENSHTEIN_COSTS, anchored=False):
+    """levenshtein_search_cross_many for needles of at most 64 bytes (ta_levenshtein_search_cross_with_opts): the same list."""
+    from . import batch as B
+    return _search_cross_many(B.levenshtein_search_cross_with_opts, needles, haystacks, k, costs, anchored)
+
+
+def levenshtein_search_nearest_with_opts_many(needles, haystacks, k, costs=LEVENSHTEIN_COSTS, anchored=False):
+    """levenshtein_search_nearest_many for needles of at most 64 bytes (ta_levenshtein_search_cross_with_opts): the same list."""
+    from . import batch as B
+    return _search_nearest_many(B.levenshtein_search_cross_with_opts, needles, haystacks, k, costs, anchored)
 
 
 def _hsx_panic(per):

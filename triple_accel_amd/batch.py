@@ -607,18 +607,8 @@ def cross_to_arrays(hits, count, allow_cut=False):
     return h[:, 0].copy(), h[:, 1].copy(), h[:, 2].copy()
 
 
-def levenshtein_search_cross(needles: Strings, haystacks: Strings, k, costs=LEVENSHTEIN_COSTS, anchored=False, cap=None, hits=None, count=None,
-                             nearest=False, best=False, per_haystack=False):
-    """Every needle of a panel searched in every haystack within k, on the device (ta_levenshtein_search_cross): -> (hits, count, nearest,
-    best, per_haystack).  For needle p and haystack i let R = levenshtein_search_simd_with_opts(needle p, haystack i, k, SearchType.Best,
-    costs, anchored): the pair is a hit exactly when R is not empty.  count (int64, one element) = the number of hits whatever cap is;
-    hits[:min(count, cap)] = that many distinct hits as int32 (haystack, needle, R[0].start, R[0].end, R[0].k, len(R)) rows in no
-    particular order (search_cross_to_arrays sorts them).  cap = 0: the count only.  nearest = True (or an int64 tensor of haystacks.n
-    elements to reuse): nearest[i] = R[0].k << 32 | p of haystack i's cheapest needle -- at equal cost the lowest index -- and -1 where no
-    needle hits.  best = True (or an int64 (haystacks.n, 3) tensor): that needle's R[0] as a (start, end, k) row, (0, 0, 0xFFFFFFFF) where
-    no needle hits; it does not need nearest.  per_haystack = True (or an int32 tensor): the number of needles that hit haystack i.  None
-    of the three depends on cap; each is None when not asked for.  Needles of at most 32 bytes, at most 65,535 of them.  Default cap: room
-    for eight hits per haystack (at least 1,024, at most every pair).  Nothing is synchronised: read count before trusting hits."""
+def _search_cross_call(entry, needles, haystacks, k, costs, anchored, cap, hits, count, nearest, best, per_haystack):
+    """the buffers, the call and the status of both levenshtein_search_cross entries; entry(*leading, *trailing arguments) -> status"""
     nn, nh, dev = needles.n, haystacks.n, haystacks.blob.device
     if cap is None:
         cap = hits.numel() // 6 if hits is not None else min(nn * nh, max(1024, 8 * nh))
@@ -633,13 +623,39 @@ def levenshtein_search_cross(needles: Strings, haystacks: Strings, k, costs=LEVE
     assert best is None or (best.dtype == torch.int64 and best.is_contiguous() and best.numel() >= nh * 3)
     assert per_haystack is None or (per_haystack.dtype == torch.int32 and per_haystack.is_contiguous() and per_haystack.numel() >= nh)
     cc = _costs(costs)._c()
-    rc = _n.lib().ta_levenshtein_search_cross(needles._ref(), nn, haystacks._ref(), nh, int(k), _C.byref(cc), int(bool(anchored)),
-                                              hits.data_ptr() if cap else None, count.data_ptr(), cap,
-                                              None if nearest is None else nearest.data_ptr(), None if best is None else best.data_ptr(),
-                                              None if per_haystack is None else per_haystack.data_ptr(), _stream())
+    rc = entry((needles._ref(), nn, haystacks._ref(), nh, int(k), _C.byref(cc), int(bool(anchored))),
+               (hits.data_ptr() if cap else None, count.data_ptr(), cap,
+                None if nearest is None else nearest.data_ptr(), None if best is None else best.data_ptr(),
+                None if per_haystack is None else per_haystack.data_ptr(), _stream()))
     if rc:
         _raise(rc)
     return hits, count, nearest, best, per_haystack
+
+
+def levenshtein_search_cross(needles: Strings, haystacks: Strings, k, costs=LEVENSHTEIN_COSTS, anchored=False, cap=None, hits=None, count=None,
+                             nearest=False, best=False, per_haystack=False):
+    """Every needle of a panel searched in every haystack within k, on the device (ta_levenshtein_search_cross): -> (hits, count, nearest,
+    best, per_haystack).  For needle p and haystack i let R = levenshtein_search_simd_with_opts(needle p, haystack i, k, SearchType.Best,
+    costs, anchored): the pair is a hit exactly when R is not empty.  count (int64, one element) = the number of hits whatever cap is;
+    hits[:min(count, cap)] = that many distinct hits as int32 (haystack, needle, R[0].start, R[0].end, R[0].k, len(R)) rows in no
+    particular order (search_cross_to_arrays sorts them).  cap = 0: the count only.  nearest = True (or an int64 tensor of haystacks.n
+    elements to reuse): nearest[i] = R[0].k << 32 | p of haystack i's cheapest needle -- at equal cost the lowest index -- and -1 where no
+    needle hits.  best = True (or an int64 (haystacks.n, 3) tensor): that needle's R[0] as a (start, end, k) row, (0, 0, 0xFFFFFFFF) where
+    no needle hits; it does not need nearest.  per_haystack = True (or an int32 tensor): the number of needles that hit haystack i.  None
+    of the three depends on cap; each is None when not asked for.  Needles of at most 32 bytes, at most 65,535 of them.  Default cap: room
+    for eight hits per haystack (at least 1,024, at most every pair).  Nothing is synchronised: read count before trusting hits."""
+    return _search_cross_call(lambda a, b: _n.lib().ta_levenshtein_search_cross(*a, *b), needles, haystacks, k, costs, anchored, cap, hits, count,
+                              nearest, best, per_haystack)
+
+
+def levenshtein_search_cross_with_opts(needles: Strings, haystacks: Strings, k, costs=LEVENSHTEIN_COSTS, anchored=False, cap=None, hits=None,
+                                       count=None, nearest=False, best=False, per_haystack=False):
+    """levenshtein_search_cross for needles of at most 64 bytes (ta_levenshtein_search_cross_with_opts, its flags word 0): the same
+    arguments, the same five results, the same exceptions.  A panel whose longest needle is at most 32 bytes runs the same kernels as
+    levenshtein_search_cross; a longer one takes the two-word route as a whole -- a few long adapters beside many short barcodes are
+    better served by one call of each entry."""
+    return _search_cross_call(lambda a, b: _n.lib().ta_levenshtein_search_cross_with_opts(*a, 0, *b), needles, haystacks, k, costs, anchored, cap,
+                              hits, count, nearest, best, per_haystack)
 
 
 def search_cross_to_arrays(hits, count, allow_cut=False):

@@ -92,9 +92,10 @@ TA_HD inline bool sx_wins(const SxRec &r, uint64_t nearest) { return r.k != TA_N
 struct SxPlan {
     uint32_t groups, hpw, sub;
 };
-inline SxPlan sx_plan(uint64_t nn, uint64_t nh, uint64_t forced) {
+// group: the needles of one scan group (the two-word route's groups are 32 needles, lev_search_cross_w2_body.h).
+inline SxPlan sx_plan(uint64_t nn, uint64_t nh, uint64_t forced, uint32_t group = SX_GROUP) {
     SxPlan p;
-    p.groups = (uint32_t)((nn + SX_GROUP - 1) / SX_GROUP);
+    p.groups = (uint32_t)((nn + group - 1) / group);
     uint64_t sub_max = SX_BUDGET / sizeof(SxRec) / (nn ? nn : 1);            // >= 204: nn <= 65,535
     if (forced && forced < sub_max) sub_max = forced;
     if (sub_max > nh) sub_max = nh;

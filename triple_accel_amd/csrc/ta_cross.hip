@@ -1,6 +1,7 @@
-// ta_cross.hip -- ta_levenshtein_cross, ta_levenshtein_cross_with_opts, ta_hamming_cross, ta_levenshtein_search_cross and ta_hamming_search_cross
-// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.17): validation, the length bounds, the query tile / the sub-batches and the launches of
-// lev_cross.hip / lev_cross_win.hip / ham_cross.hip / lev_search_cross.hip / ham_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
+// ta_cross.hip -- ta_levenshtein_cross, ta_levenshtein_cross_with_opts, ta_hamming_cross, ta_levenshtein_search_cross,
+// ta_levenshtein_search_cross_with_opts and ta_hamming_search_cross
+// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.18): validation, the length bounds, the query tile / the sub-batches and the launches of
+// lev_cross.hip / lev_cross_win.hip / ham_cross.hip / lev_search_cross.hip / lev_search_cross_w2.hip / ham_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
 // there is no synchronisation and the call can be captured into a graph.  The shared host rules (cost check and scale, length bounds,
 // measured maxima) and the scratch slots' names (SLOT_CROSS_CTL, SLOT_SX_*) are those of ta_internal.h; the query tile's rule is
 // lev_plan.h's cross_qtile, the sub-batches' lev_search_cross_body.h's sx_plan.
@@ -9,7 +10,7 @@
 
 #include "ham_search_cross_body.h"
 #include "lev_cross_win_body.h"
-#include "lev_search_cross_body.h"
+#include "lev_search_cross_w2_body.h"
 #include "ta_internal.h"
 
 namespace ta {
@@ -53,9 +54,13 @@ static int cross_fill64(unsigned long long *p, uint32_t half, uint64_t n, hipStr
     return TA_OK;
 }
 
-// the limits of ta_levenshtein_search_cross and ta_hamming_search_cross over the counts and the length bounds known so far (0: not known yet)
-static int search_cross_limits(uint64_t nn, uint64_t nh, uint64_t max_needle, uint64_t max_hay) {
-    if (max_needle > SX_MAX_NEEDLE) { set_last_error_msg("search cross: a needle longer than 32 bytes"); return TA_ERR_UNSUPPORTED; }
+// the limits of the search cross entries over the counts and the length bounds known so far (0: not known yet); max_needle_limit: the
+// entry's limit on a needle's length (32, or 64 for ta_levenshtein_search_cross_with_opts)
+static int search_cross_limits(uint64_t nn, uint64_t nh, uint64_t max_needle, uint64_t max_hay, uint32_t max_needle_limit = SX_MAX_NEEDLE) {
+    if (max_needle > max_needle_limit) {
+        set_last_error_msg(max_needle_limit > SX_MAX_NEEDLE ? "search cross: a needle longer than 64 bytes" : "search cross: a needle longer than 32 bytes");
+        return TA_ERR_UNSUPPORTED;
+    }
     if (nn > 65535u) { set_last_error_msg("search cross: more than 65,535 needles"); return TA_ERR_UNSUPPORTED; }
     if (max_hay >> 32 || nh >> 32) { set_last_error_msg("search cross: a haystack of 2^32 bytes or more, or 2^32 or more haystacks"); return TA_ERR_UNSUPPORTED; }
     return TA_OK;
@@ -167,16 +172,20 @@ extern "C" int ta_hamming_cross(const ta_strings *queries, size_t nq, const ta_s
     return TA_OK;
 }
 
-extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
-                                           uint32_t k, const ta_edit_costs *costs, int anchored,
-                                           ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
-                                           uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+// ta_levenshtein_search_cross and ta_levenshtein_search_cross_with_opts: one host path.  max_needle_limit: the entry's limit on a needle's
+// length; flags: the reserved word of the with_opts entry (the other passes 0), checked right behind the NULL pointers.
+static int search_cross_run(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                            uint32_t k, const ta_edit_costs *costs, int anchored, uint32_t flags, uint32_t max_needle_limit,
+                            ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                            uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
     if (!costs || !needles || !haystacks || !count_dev) { set_last_error_msg("null costs / needles / haystacks / count_dev"); return TA_ERR_ARG; }
+    if (flags) { set_last_error_msg("levenshtein search cross: unknown flag bits (the word is reserved: 0)"); return TA_ERR_ARG; }
     if (!costs_ok(costs) || ta_edit_costs_check_search(costs) != TA_OK) return TA_ERR_BAD_COSTS;   // EditCosts::new; :1965, for the whole call
     if (nn && nh && (!needles->blob || !haystacks->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
     if (cap && !hits_dev) { set_last_error_msg("cap > 0 with null hits_dev"); return TA_ERR_ARG; }
     if (cap > SIZE_MAX / sizeof(ta_search_cross_hit)) { set_last_error_msg("cap * sizeof(ta_search_cross_hit) overflows"); return TA_ERR_ARG; }
-    int rc = search_cross_limits(nn, nh, side_bound_known(needles) ? side_bound(needles) : 0, side_bound_known(haystacks) ? side_bound(haystacks) : 0);
+    int rc = search_cross_limits(nn, nh, side_bound_known(needles) ? side_bound(needles) : 0, side_bound_known(haystacks) ? side_bound(haystacks) : 0,
+                                 max_needle_limit);
     if (rc) return rc;
     if (!device_ready()) return TA_ERR_HIP;
     hipStream_t st = (hipStream_t)stream;
@@ -197,7 +206,7 @@ extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn,
     if ((rc = ctl.ensure(64))) return rc;
     uint64_t max_n = 0, max_h = 0;
     if ((rc = measure_max_lens(needles, (uint32_t)nn, haystacks, (uint32_t)nh, (unsigned long long *)ctl.dev + 2, st, &max_n, &max_h))) return rc;
-    if ((rc = search_cross_limits(nn, nh, max_n, max_h))) return rc;
+    if ((rc = search_cross_limits(nn, nh, max_n, max_h, max_needle_limit))) return rc;
 
     SearchCrossParams P = {};
     P.nd = view_of(needles); P.hs = view_of(haystacks);
@@ -207,9 +216,12 @@ extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn,
     P.anchored = anchored ? 1u : 0u;
     P.max_needle = (uint32_t)max_n;
     const bool trans = costs->has_transpose != 0;
+    // The route, once per call from the longest-needle bound: up to 32 bytes the one-word kernels (lev_search_cross.hip), beyond them the
+    // two-word ones for the whole panel (lev_search_cross_w2.hip) -- groups of 32 needles, the exact pass's column in memory
+    const bool w2 = max_n > SX_MAX_NEEDLE;
     // the scan's threshold and the packed form's conditions: ta_levenshtein_search_batch's (ta_search_batch.hip)
     P.kf = costs_unit(costs) ? k : srch_filter_k(k, P.mc, P.gc, P.sg, trans, P.tc);
-    const uint64_t halo = max_n + P.kf + 2;                                             // (only needles with kf < n <= 32 use it)
+    const uint64_t halo = max_n + P.kf + 2;                                             // (only needles with kf < n use it)
     P.halo = halo > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)halo;
     const uint32_t unit_k = lev_sat_sub(k, P.sg) / P.gc;
     const uint64_t cols = anchored ? (max_h < max_n + unit_k ? max_h : max_n + unit_k) : max_h;
@@ -219,10 +231,16 @@ extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn,
 
     // Sub-batches of whole workgroups: the records of one stay within SX_BUDGET; their number depends on nn, nh and the budget only
     const int forced = env_int("TA_SEARCH_CROSS_SUB");
-    const SxPlan plan = sx_plan(nn, nh, forced > 0 ? (uint64_t)forced : 0);
+    const SxPlan plan = sx_plan(nn, nh, forced > 0 ? (uint64_t)forced : 0, w2 ? SX2_GROUP : SX_GROUP);
     Scratch &rs = tls_scratch(SLOT_SX_REC);
     if ((rc = rs.ensure((size_t)plan.sub * nn * sizeof(SxRec)))) return rc;
     P.rec = (SxRec *)rs.dev;
+    if (w2) {                          // one memory-backed column per resident lane of the exact pass, within SX_BUDGET (from nn and nh alone)
+        P.col_lanes = sx2_exact_lanes((uint64_t)plan.sub * nn);
+        Scratch &cs = tls_scratch(SLOT_SX_COL);
+        if ((rc = cs.ensure((size_t)P.col_lanes * SX2_COL_WORDS * sizeof(uint32_t)))) return rc;
+        P.col = (uint32_t *)cs.dev;
+    }
     P.hpw = plan.hpw;
     P.n_rec = anchored ? nullptr : (uint32_t *)ctl.dev;
     for (uint64_t h0 = 0; h0 < nh; h0 += plan.sub) {
@@ -230,13 +248,29 @@ extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn,
         P.h1 = (uint32_t)(h0 + plan.sub < nh ? h0 + plan.sub : nh);
         if (!anchored) {
             TA_HIP(fill_u32_launch(P.n_rec, 0u, 1, st));
-            TA_HIP(search_cross_scan_launch(P, trans, st));
+            TA_HIP(w2 ? search_cross_w2_scan_launch(P, trans, st) : search_cross_scan_launch(P, trans, st));
         }
-        TA_HIP(search_cross_exact_launch(P, trans, packed, st));
+        TA_HIP(w2 ? search_cross_w2_exact_launch(P, trans, st) : search_cross_exact_launch(P, trans, packed, st));
         TA_HIP(search_cross_finish_launch(P, st));
     }
-    if (!anchored) set_last_kernel_name("lev_search_cross_scan_kernel<%s>", trans ? "true" : "false");
+    if (!anchored) set_last_kernel_name(w2 ? "lev_search_cross_w2_scan_kernel<%s>" : "lev_search_cross_scan_kernel<%s>", trans ? "true" : "false");
     return TA_OK;
+}
+
+extern "C" int ta_levenshtein_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                           uint32_t k, const ta_edit_costs *costs, int anchored,
+                                           ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                           uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+    return search_cross_run(needles, nn, haystacks, nh, k, costs, anchored, 0u, SX_MAX_NEEDLE, hits_dev, count_dev, cap, nearest_dev, best_dev,
+                            per_haystack_dev, stream);
+}
+
+extern "C" int ta_levenshtein_search_cross_with_opts(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                                     uint32_t k, const ta_edit_costs *costs, int anchored, uint32_t flags,
+                                                     ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                                     uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+    return search_cross_run(needles, nn, haystacks, nh, k, costs, anchored, flags, SX2_MAX_NEEDLE, hits_dev, count_dev, cap, nearest_dev, best_dev,
+                            per_haystack_dev, stream);
 }
 
 extern "C" int ta_hamming_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,

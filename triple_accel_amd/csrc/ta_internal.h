@@ -88,12 +88,15 @@ enum ScratchSlot {
     SLOT_CROSS_CTL = 30,     // ta_cross.hip: measure_max_lens' two 64-bit words.  Alone.
     SLOT_SX_CTL = 31,        // ta_levenshtein_search_cross: word 0 the candidate count of the sub-batch in flight; words 4..7: measure_max_lens.
     SLOT_SX_REC = 32,        // ... the candidate / result records of one sub-batch (at most SX_BUDGET bytes),
-    SLOT_SX_NEAR = 33,       // ... and the nearest words when the caller asks for best_dev without nearest_dev.  31..33: that entry alone.
+    SLOT_SX_NEAR = 33,       // ... and the nearest words when the caller asks for best_dev without nearest_dev.  31..33: that entry and
+                             // ta_levenshtein_search_cross_with_opts (one host path; neither calls the other).
     SLOT_HSX_CTL = 34,       // ta_hamming_search_cross: measure_max_lens' two 64-bit words ...
     SLOT_HSX_WORD = 35,      // ... and the packed nearest words (d << 48 | needle << 32 | start), one per haystack, live from the fill to the
                              // finish kernel.  34, 35: that entry alone.
     SLOT_HAM_LONG = 36,      // ham_long.hip: the plan of a CSR batch and the per-slice counts, dead once the finish kernel has run (ta_hamming_batch,
                              // ta_hamming_dev, the chunked ta_hamming).  Alone.
+    SLOT_SX_COL = 37,        // ta_levenshtein_search_cross_with_opts, needles beyond 32 bytes: the exact pass's memory-backed columns, one per
+                             // resident lane (at most SX_BUDGET bytes), dead once a sub-batch's exact kernel has run.  That entry alone.
     TA_SCRATCH_SLOTS
 };
 Scratch &tls_scratch(ScratchSlot which);
@@ -406,10 +409,11 @@ struct HamCrossParams {
 };
 hipError_t ham_cross_launch(const HamCrossParams &P, int nw, hipStream_t st);
 
-// ta_levenshtein_search_cross (lev_search_cross.hip): every needle of a panel in every haystack, one sub-batch of haystacks per launch
+// ta_levenshtein_search_cross and ta_levenshtein_search_cross_with_opts (lev_search_cross.hip; needles beyond 32 bytes:
+// lev_search_cross_w2.hip): every needle of a panel in every haystack, one sub-batch of haystacks per launch
 struct SxRec;
 struct SearchCrossParams {
-    StrView nd, hs;               // needles (every one at most 32 bytes), haystacks
+    StrView nd, hs;               // needles (every one at most 32 bytes; the two-word route: 64), haystacks
     uint32_t nn;
     uint32_t h0, h1;              // the sub-batch: haystacks [h0, h1)
     uint32_t hpw;                 // haystacks per scan workgroup
@@ -424,11 +428,15 @@ struct SearchCrossParams {
     unsigned long long *nearest;  // device: nh words preset to all ones, or nullptr
     uint32_t *per_haystack;       // device: nh words pre-zeroed, or nullptr
     ta_match *best;               // device: nh records preset to {0, 0, TA_NONE, 0}, or nullptr
+    uint32_t *col;                // the two-word route: device, col_lanes memory-backed columns of 6 x 65 words (element-major), else nullptr
+    uint32_t col_lanes;           // ... the exact pass's grid in lanes, a multiple of 256
 };
 hipError_t search_cross_init_best_launch(ta_match *best, uint32_t nh, hipStream_t st);
 hipError_t search_cross_scan_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
 hipError_t search_cross_exact_launch(const SearchCrossParams &P, bool trans, bool packed, hipStream_t st);
 hipError_t search_cross_finish_launch(const SearchCrossParams &P, hipStream_t st);
+hipError_t search_cross_w2_scan_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
+hipError_t search_cross_w2_exact_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
 
 // ta_hamming_search_cross (ham_search_cross.hip): every needle of a panel in every haystack, substitutions only, in one launch
 struct HamSearchCrossParams {
