@@ -529,6 +529,29 @@ int ta_hamming_search_cross(const ta_strings *needles, size_t nn, const ta_strin
                             ta_match *best_dev         /* nh entries, or NULL */,
                             uint32_t *per_haystack_dev /* nh entries, or NULL */, void *stream);
 
+/* ta_hamming_search_cross for panels with needles of up to 64 bytes: read-through adapters (33, 34 bytes), full-length indexed adapters,
+ * primer-plus-tag constructs of 40 to 64 bytes, where "at most k mismatches, no indels" is the rule (the reference searches one needle in
+ * one haystack per call, src/hamming.rs:454-475, scalar text :96-146; R(p, i) is the same list: the windows at the smallest mismatch
+ * count <= k, in increasing start, no overlap fold).  The contract is ta_hamming_search_cross's word for word -- R(p, i), records, count,
+ * cap, cap = 0, nearest_dev, best_dev, per_haystack_dev, the per-pair order of the checks (needle_len > haystack_len, needle_len == 0,
+ * then the 0x00 rule with per_haystack_dev[i] = TA_NONE), both string forms at any alignment, empty sides, asynchrony, capture, every
+ * output initialised by kernels -- with two differences:
+ *   1. every NEEDLE is at most 64 bytes: a longer bound (the strided len, the CSR max_len given or measured) is TA_ERR_UNSUPPORTED;
+ *   2. `flags` must be 0: any set bit is TA_ERR_ARG (the word is reserved), checked behind the NULL pointers and before the blobs.
+ * The error order is otherwise the same: NULL pointers, flags, blobs / cap / overflow, the limits, TA_ERR_HIP.
+ * Routes, decided once per call from the panel's longest-needle bound.  Up to 32 bytes: exactly the kernel, the work split and the
+ * ta_last_kernel_name of ta_hamming_search_cross (ham_search_cross_kernel<B>).  33..64 bytes: the two-word route for the WHOLE panel
+ *  -- mismatch counters of 64 positions on two dwords against 32 needles per half wavefront, still one exact pass
+ * without a candidate list: ham_search_cross_w2_kernel<B>, B = the smallest with 2^B - 1 >= min(k, longest needle): 1 .. 7.  The word
+ * count is not chosen per group of needles (a CSR panel's lengths are known on the device only), so short barcodes in a long panel pay
+ * for two words: a caller with 96 barcodes and 2 long adapters does better with two calls, one per entry. */
+int ta_hamming_search_cross_with_opts(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                      uint32_t k, uint32_t flags,
+                                      ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                      uint64_t *nearest_dev      /* nh entries, or NULL */,
+                                      ta_match *best_dev         /* nh entries, or NULL */,
+                                      uint32_t *per_haystack_dev /* nh entries, or NULL */, void *stream);
+
 /* ---- token batches: sequences of 32-bit items (new surface) ----------------------------------
  * The generic entry points of the reference take any item type T: PartialEq (levenshtein_naive<T>, levenshtein_naive_with_opts<T>,
  * levenshtein_naive_k_with_opts<T>, src/levenshtein.rs:105-148, 376).  These entries extend the batch contracts above to sequences of

@@ -523,6 +523,28 @@ def _hsx_panic(per):
         raise PanicError("No zero/null bytes allowed in the string! (haystack %d)" % nul[0])
 
 
+def _hamming_search_cross_many(entry, needles, haystacks, k):
+    from . import batch as B
+    nd, hs = _cross_sides(needles, haystacks)
+    k = _k(k)
+    hits, count, _, _, per = entry(nd, hs, k, per_haystack=True)
+    n = int(count.cpu()[0].item())
+    if n > hits.shape[0]:
+        hits, count, _, _, per = entry(nd, hs, k, cap=n, per_haystack=True)
+    _hsx_panic(per.cpu().numpy().view("uint32"))
+    cols = B.search_cross_to_arrays(hits, count)
+    return [(int(i), int(p), Match(int(s), int(e), int(d)), int(m)) for i, p, s, e, d, m in zip(*cols)]
+
+
+def _hamming_search_nearest_many(entry, needles, haystacks, k):
+    nd, hs = _cross_sides(needles, haystacks)
+    _, _, nearest, best, per = entry(nd, hs, _k(k), cap=0, nearest=True, best=True, per_haystack=True)
+    words, rows, counts = nearest.cpu().numpy().view("uint64"), best.cpu().numpy(), per.cpu().numpy().view("uint32")
+    _hsx_panic(counts)
+    return [(None, None, 0) if int(w) == 0xFFFFFFFFFFFFFFFF else
+            (int(w) & 0xFFFFFFFF, Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF), int(c)) for w, r, c in zip(words, rows, counts)]
+
+
 def hamming_search_cross_many(needles, haystacks, k):
     """Every needle searched in every haystack in ONE device call (ta_hamming_search_cross): the sorted list of (haystack, needle, Match,
     n_matches) for every pair where R = hamming_search_simd_with_opts(needles[p], haystacks[i], k, SearchType.Best) is not empty, with
@@ -530,15 +552,7 @@ def hamming_search_cross_many(needles, haystacks, k):
     some non-empty needle).  Needles of at most 32 bytes.  Both lists are uploaded; when there are more hits than the first call's room,
     one more call runs with room for the count it reported."""
     from . import batch as B
-    nd, hs = _cross_sides(needles, haystacks)
-    k = _k(k)
-    hits, count, _, _, per = B.hamming_search_cross(nd, hs, k, per_haystack=True)
-    n = int(count.cpu()[0].item())
-    if n > hits.shape[0]:
-        hits, count, _, _, per = B.hamming_search_cross(nd, hs, k, cap=n, per_haystack=True)
-    _hsx_panic(per.cpu().numpy().view("uint32"))
-    cols = B.search_cross_to_arrays(hits, count)
-    return [(int(i), int(p), Match(int(s), int(e), int(d)), int(m)) for i, p, s, e, d, m in zip(*cols)]
+    return _hamming_search_cross_many(B.hamming_search_cross, needles, haystacks, k)
 
 
 def hamming_search_nearest_many(needles, haystacks, k):
@@ -547,12 +561,19 @@ def hamming_search_nearest_many(needles, haystacks, k):
     equal count the lowest needle index.  needles that hit == 1 is the demultiplexer's "exactly one barcode within k mismatches".
     Raises PanicError where a single call would."""
     from . import batch as B
-    nd, hs = _cross_sides(needles, haystacks)
-    _, _, nearest, best, per = B.hamming_search_cross(nd, hs, _k(k), cap=0, nearest=True, best=True, per_haystack=True)
-    words, rows, counts = nearest.cpu().numpy().view("uint64"), best.cpu().numpy(), per.cpu().numpy().view("uint32")
-    _hsx_panic(counts)
-    return [(None, None, 0) if int(w) == 0xFFFFFFFFFFFFFFFF else
-            (int(w) & 0xFFFFFFFF, Match(int(r[0]), int(r[1]), int(r[2]) & 0xFFFFFFFF), int(c)) for w, r, c in zip(words, rows, counts)]
+    return _hamming_search_nearest_many(B.hamming_search_cross, needles, haystacks, k)
+
+
+def hamming_search_cross_with_opts_many(needles, haystacks, k):
+    """hamming_search_cross_many for needles of at most 64 bytes (ta_hamming_search_cross_with_opts): the same list."""
+    from . import batch as B
+    return _hamming_search_cross_many(B.hamming_search_cross_with_opts, needles, haystacks, k)
+
+
+def hamming_search_nearest_with_opts_many(needles, haystacks, k):
+    """hamming_search_nearest_many for needles of at most 64 bytes (ta_hamming_search_cross_with_opts): the same list."""
+    from . import batch as B
+    return _hamming_search_nearest_many(B.hamming_search_cross_with_opts, needles, haystacks, k)
 
 
 def levenshtein_select(a_len, b_len, k, costs=LEVENSHTEIN_COSTS):

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "ta_levenshtein_cross", "ta_hamming_cross", "ta_levenshtein_cross_with_opts",
     # every needle of a panel in every haystack (ta_cross.hip)
     "ta_levenshtein_search_cross", "ta_levenshtein_search_cross_with_opts", "ta_hamming_search_cross",
+    "ta_hamming_search_cross_with_opts",
     # hamming of one long pair resident in HBM (ham_long.hip)
     "ta_hamming_dev",
 ]
@@ -209,6 +210,8 @@ def lib():
     sig("ta_levenshtein_search_cross_with_opts", i32,
         [sp, sz, sp, sz, u32, cp, i32, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("ta_hamming_search_cross", i32, [sp, sz, sp, sz, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("ta_hamming_search_cross_with_opts", i32,
+        [sp, sz, sp, sz, u32, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     _lib = L
     return L
 

@@ -671,15 +671,8 @@ def search_cross_to_arrays(hits, count, allow_cut=False):
     return tuple(h[:, c].copy() for c in range(6))
 
 
-def hamming_search_cross(needles: Strings, haystacks: Strings, k, cap=None, hits=None, count=None, nearest=False, best=False, per_haystack=False):
-    """Every needle of a panel searched in every haystack within k MISMATCHES, on the device (ta_hamming_search_cross): -> (hits, count,
-    nearest, best, per_haystack), shaped as levenshtein_search_cross's (search_cross_to_arrays reads hits and count).  For needle p and
-    haystack i let R = hamming_search_simd_with_opts(needle p, haystack i, k, SearchType.Best): the pair is a hit exactly when R is not
-    empty, its row is (haystack, needle, R[0].start, R[0].end, R[0].k, len(R)).  An empty needle never hits.  Where the single call
-    panics -- a NUL byte in a haystack that is not shorter than the non-empty needle -- the pair has no row and touches neither nearest
-    nor best, and per_haystack[i] = -1 for such a haystack: a caller who cannot rule out NUL bytes asks for per_haystack.  The other
-    haystacks are unaffected.  Needles of at most 32 bytes, at most 65,535 of them.  Default cap: room for eight hits per haystack (at
-    least 1,024, at most every pair).  Nothing is synchronised: read count before trusting hits."""
+def _hamming_search_cross_call(entry, needles, haystacks, k, cap, hits, count, nearest, best, per_haystack):
+    """hamming_search_cross and hamming_search_cross_with_opts: entry(a, b) calls the C function with a = (needles .. k), b = (hits ..)"""
     nn, nh, dev = needles.n, haystacks.n, haystacks.blob.device
     if cap is None:
         cap = hits.numel() // 6 if hits is not None else min(nn * nh, max(1024, 8 * nh))
@@ -693,10 +686,32 @@ def hamming_search_cross(needles: Strings, haystacks: Strings, k, cap=None, hits
     assert nearest is None or (nearest.dtype == torch.int64 and nearest.is_contiguous() and nearest.numel() >= nh)
     assert best is None or (best.dtype == torch.int64 and best.is_contiguous() and best.numel() >= nh * 3)
     assert per_haystack is None or (per_haystack.dtype == torch.int32 and per_haystack.is_contiguous() and per_haystack.numel() >= nh)
-    rc = _n.lib().ta_hamming_search_cross(needles._ref(), nn, haystacks._ref(), nh, int(k), hits.data_ptr() if cap else None,
-                                          count.data_ptr(), cap, None if nearest is None else nearest.data_ptr(),
-                                          None if best is None else best.data_ptr(),
-                                          None if per_haystack is None else per_haystack.data_ptr(), _stream())
+    rc = entry((needles._ref(), nn, haystacks._ref(), nh, int(k)),
+               (hits.data_ptr() if cap else None, count.data_ptr(), cap, None if nearest is None else nearest.data_ptr(),
+                None if best is None else best.data_ptr(), None if per_haystack is None else per_haystack.data_ptr(), _stream()))
     if rc:
         _raise(rc)
     return hits, count, nearest, best, per_haystack
+
+
+def hamming_search_cross(needles: Strings, haystacks: Strings, k, cap=None, hits=None, count=None, nearest=False, best=False, per_haystack=False):
+    """Every needle of a panel searched in every haystack within k MISMATCHES, on the device (ta_hamming_search_cross): -> (hits, count,
+    nearest, best, per_haystack), shaped as levenshtein_search_cross's (search_cross_to_arrays reads hits and count).  For needle p and
+    haystack i let R = hamming_search_simd_with_opts(needle p, haystack i, k, SearchType.Best): the pair is a hit exactly when R is not
+    empty, its row is (haystack, needle, R[0].start, R[0].end, R[0].k, len(R)).  An empty needle never hits.  Where the single call
+    panics -- a NUL byte in a haystack that is not shorter than the non-empty needle -- the pair has no row and touches neither nearest
+    nor best, and per_haystack[i] = -1 for such a haystack: a caller who cannot rule out NUL bytes asks for per_haystack.  The other
+    haystacks are unaffected.  Needles of at most 32 bytes, at most 65,535 of them.  Default cap: room for eight hits per haystack (at
+    least 1,024, at most every pair).  Nothing is synchronised: read count before trusting hits."""
+    return _hamming_search_cross_call(lambda a, b: _n.lib().ta_hamming_search_cross(*a, *b), needles, haystacks, k, cap, hits, count, nearest,
+                                      best, per_haystack)
+
+
+def hamming_search_cross_with_opts(needles: Strings, haystacks: Strings, k, cap=None, hits=None, count=None, nearest=False, best=False,
+                                   per_haystack=False):
+    """hamming_search_cross for needles of at most 64 bytes (ta_hamming_search_cross_with_opts, its flags word 0): the same arguments, the
+    same five results, the same exceptions.  A panel whose longest needle is at most 32 bytes runs the same kernel as
+    hamming_search_cross; a longer one takes the two-word route as a whole -- a few long adapters beside many short barcodes are better
+    served by one call of each entry."""
+    return _hamming_search_cross_call(lambda a, b: _n.lib().ta_hamming_search_cross_with_opts(*a, 0, *b), needles, haystacks, k, cap, hits,
+                                      count, nearest, best, per_haystack)

@@ -1,14 +1,15 @@
 // ta_cross.hip -- ta_levenshtein_cross, ta_levenshtein_cross_with_opts, ta_hamming_cross, ta_levenshtein_search_cross,
-// ta_levenshtein_search_cross_with_opts and ta_hamming_search_cross
-// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.18): validation, the length bounds, the query tile / the sub-batches and the launches of
-// lev_cross.hip / lev_cross_win.hip / ham_cross.hip / lev_search_cross.hip / lev_search_cross_w2.hip / ham_search_cross.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
+// ta_levenshtein_search_cross_with_opts, ta_hamming_search_cross and ta_hamming_search_cross_with_opts
+// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.19): validation, the length bounds, the query tile / the sub-batches and the launches of
+// lev_cross.hip / lev_cross_win.hip / ham_cross.hip / lev_search_cross.hip / lev_search_cross_w2.hip / ham_search_cross.hip /
+// ham_search_cross_w2.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
 // there is no synchronisation and the call can be captured into a graph.  The shared host rules (cost check and scale, length bounds,
 // measured maxima) and the scratch slots' names (SLOT_CROSS_CTL, SLOT_SX_*) are those of ta_internal.h; the query tile's rule is
 // lev_plan.h's cross_qtile, the sub-batches' lev_search_cross_body.h's sx_plan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ham_search_cross_body.h"
+#include "ham_search_cross_w2_body.h"
 #include "lev_cross_win_body.h"
 #include "lev_search_cross_w2_body.h"
 #include "ta_internal.h"
@@ -55,7 +56,7 @@ static int cross_fill64(unsigned long long *p, uint32_t half, uint64_t n, hipStr
 }
 
 // the limits of the search cross entries over the counts and the length bounds known so far (0: not known yet); max_needle_limit: the
-// entry's limit on a needle's length (32, or 64 for ta_levenshtein_search_cross_with_opts)
+// entry's limit on a needle's length (32, or 64 for the two with_opts entries)
 static int search_cross_limits(uint64_t nn, uint64_t nh, uint64_t max_needle, uint64_t max_hay, uint32_t max_needle_limit = SX_MAX_NEEDLE) {
     if (max_needle > max_needle_limit) {
         set_last_error_msg(max_needle_limit > SX_MAX_NEEDLE ? "search cross: a needle longer than 64 bytes" : "search cross: a needle longer than 32 bytes");
@@ -273,15 +274,19 @@ extern "C" int ta_levenshtein_search_cross_with_opts(const ta_strings *needles, 
                             per_haystack_dev, stream);
 }
 
-extern "C" int ta_hamming_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
-                                       uint32_t k,
-                                       ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
-                                       uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+// ta_hamming_search_cross and ta_hamming_search_cross_with_opts: one host path.  max_needle_limit: the entry's limit on a needle's length;
+// flags: the reserved word of the with_opts entry (the other passes 0), checked right behind the NULL pointers.
+static int ham_search_cross_run(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                uint32_t k, uint32_t flags, uint32_t max_needle_limit,
+                                ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
     if (!needles || !haystacks || !count_dev) { set_last_error_msg("null needles / haystacks / count_dev"); return TA_ERR_ARG; }
+    if (flags) { set_last_error_msg("hamming search cross: unknown flag bits (the word is reserved: 0)"); return TA_ERR_ARG; }
     if (nn && nh && (!needles->blob || !haystacks->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
     if (cap && !hits_dev) { set_last_error_msg("cap > 0 with null hits_dev"); return TA_ERR_ARG; }
     if (cap > SIZE_MAX / sizeof(ta_search_cross_hit)) { set_last_error_msg("cap * sizeof(ta_search_cross_hit) overflows"); return TA_ERR_ARG; }
-    int rc = search_cross_limits(nn, nh, side_bound_known(needles) ? side_bound(needles) : 0, side_bound_known(haystacks) ? side_bound(haystacks) : 0);
+    int rc = search_cross_limits(nn, nh, side_bound_known(needles) ? side_bound(needles) : 0, side_bound_known(haystacks) ? side_bound(haystacks) : 0,
+                                 max_needle_limit);
     if (rc) return rc;
     if (!device_ready()) return TA_ERR_HIP;
     hipStream_t st = (hipStream_t)stream;
@@ -297,7 +302,7 @@ extern "C" int ta_hamming_search_cross(const ta_strings *needles, size_t nn, con
     if ((rc = ctl.ensure(64))) return rc;
     uint64_t max_n = 0, max_h = 0;
     if ((rc = measure_max_lens(needles, (uint32_t)nn, haystacks, (uint32_t)nh, (unsigned long long *)ctl.dev, st, &max_n, &max_h))) return rc;
-    if ((rc = search_cross_limits(nn, nh, max_n, max_h))) return rc;
+    if ((rc = search_cross_limits(nn, nh, max_n, max_h, max_needle_limit))) return rc;
 
     HamSearchCrossParams P = {};
     P.nd = view_of(needles); P.hs = view_of(haystacks);
@@ -312,9 +317,29 @@ extern "C" int ta_hamming_search_cross(const ta_strings *needles, size_t nn, con
         P.packed = (unsigned long long *)ws.dev;
         if ((rc = cross_fill64(P.packed, 0xFFFFFFFFu, nh, st))) return rc;
     }
+    // The route, once per call from the longest-needle bound: up to 32 bytes the one-word kernel (ham_search_cross.hip), beyond them the
+    // two-word one for the whole panel (ham_search_cross_w2.hip) -- groups of 32 needles, two haystacks or more per wavefront step
+    const bool w2 = max_n > SX_MAX_NEEDLE;
     const int forced = env_int("TA_HSEARCH_CROSS_HPW");
-    P.hpw = hsx_hpw(nn, nh, forced > 0 ? (uint64_t)forced : 0);
-    TA_HIP(ham_search_cross_launch(P, st));                                          // (names the kernel: ham_search_cross_kernel<B>)
+    P.hpw = w2 ? hsx2_hpw(nn, nh, forced > 0 ? (uint64_t)forced : 0) : hsx_hpw(nn, nh, forced > 0 ? (uint64_t)forced : 0);
+    // (names the kernel: ham_search_cross_kernel<B> / ham_search_cross_w2_kernel<B>)
+    TA_HIP(w2 ? ham_search_cross_w2_launch(P, st) : ham_search_cross_launch(P, st));
     TA_HIP(ham_search_cross_finish_launch(P, st));
     return TA_OK;
+}
+
+extern "C" int ta_hamming_search_cross(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                       uint32_t k,
+                                       ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                       uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+    return ham_search_cross_run(needles, nn, haystacks, nh, k, 0u, SX_MAX_NEEDLE, hits_dev, count_dev, cap, nearest_dev, best_dev, per_haystack_dev,
+                                stream);
+}
+
+extern "C" int ta_hamming_search_cross_with_opts(const ta_strings *needles, size_t nn, const ta_strings *haystacks, size_t nh,
+                                                 uint32_t k, uint32_t flags,
+                                                 ta_search_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                                 uint64_t *nearest_dev, ta_match *best_dev, uint32_t *per_haystack_dev, void *stream) {
+    return ham_search_cross_run(needles, nn, haystacks, nh, k, flags, HSX2_MAX_NEEDLE, hits_dev, count_dev, cap, nearest_dev, best_dev,
+                                per_haystack_dev, stream);
 }

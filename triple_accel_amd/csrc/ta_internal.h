@@ -92,7 +92,8 @@ enum ScratchSlot {
                              // ta_levenshtein_search_cross_with_opts (one host path; neither calls the other).
     SLOT_HSX_CTL = 34,       // ta_hamming_search_cross: measure_max_lens' two 64-bit words ...
     SLOT_HSX_WORD = 35,      // ... and the packed nearest words (d << 48 | needle << 32 | start), one per haystack, live from the fill to the
-                             // finish kernel.  34, 35: that entry alone.
+                             // finish kernel.  34, 35: that entry and ta_hamming_search_cross_with_opts (one host path; neither calls
+                             // the other).
     SLOT_HAM_LONG = 36,      // ham_long.hip: the plan of a CSR batch and the per-slice counts, dead once the finish kernel has run (ta_hamming_batch,
                              // ta_hamming_dev, the chunked ta_hamming).  Alone.
     SLOT_SX_COL = 37,        // ta_levenshtein_search_cross_with_opts, needles beyond 32 bytes: the exact pass's memory-backed columns, one per
@@ -438,9 +439,10 @@ hipError_t search_cross_finish_launch(const SearchCrossParams &P, hipStream_t st
 hipError_t search_cross_w2_scan_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
 hipError_t search_cross_w2_exact_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
 
-// ta_hamming_search_cross (ham_search_cross.hip): every needle of a panel in every haystack, substitutions only, in one launch
+// ta_hamming_search_cross and ta_hamming_search_cross_with_opts (ham_search_cross.hip; needles beyond 32 bytes: ham_search_cross_w2.hip):
+// every needle of a panel in every haystack, substitutions only, in one launch
 struct HamSearchCrossParams {
-    StrView nd, hs;               // needles (every one at most 32 bytes), haystacks
+    StrView nd, hs;               // needles (every one at most 32 bytes; the two-word route: 64), haystacks
     uint32_t nn, nh;
     uint32_t hpw;                 // haystacks per workgroup
     uint32_t kc;                  // min(k, longest needle): the counters' threshold (ham_search_cross_body.h: hsx_threshold)
@@ -453,6 +455,7 @@ struct HamSearchCrossParams {
     ta_match *best;               // device: nh records the finish kernel writes, or nullptr
 };
 hipError_t ham_search_cross_launch(const HamSearchCrossParams &P, hipStream_t st);
+hipError_t ham_search_cross_w2_launch(const HamSearchCrossParams &P, hipStream_t st);   // a longest needle of 33..64 bytes (ham_search_cross_w2.hip)
 hipError_t ham_search_cross_finish_launch(const HamSearchCrossParams &P, hipStream_t st);
 
 // ta_multi.hip: the device set (one worker thread per entry).  multi_search_shards / multi_pair_shards: over how many of them a host
