@@ -14,21 +14,11 @@
 // (src/hamming.rs:36-47).
 #include <hip/hip_runtime.h>
 
+#include "dev_str.h"
 #include "ham_long_body.h"
 #include "ta_internal.h"
 
 namespace ta {
-
-__device__ __forceinline__ void hl_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
-    if (s.off) {
-        const uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
-        len = o1 - o0;
-    } else {
-        p = s.blob + (uint64_t)i * s.stride;
-        len = s.len;
-    }
-}
 
 // CSR batches (n <= HAM_CSR_MAX_PAIRS): the prefix sums of max(1, ceil(len_i / S)).  One block of 1,024 threads that loops.
 __global__ __launch_bounds__(1024) void ham_long_plan_kernel(StrView a, StrView b, uint32_t n, uint32_t S0, uint32_t *start) {
@@ -41,8 +31,8 @@ __global__ __launch_bounds__(1024) void ham_long_plan_kernel(StrView a, StrView 
     for (uint32_t i = t; i < n; i += 1024u) {
         const uint8_t *p;
         uint64_t la, lb;
-        hl_str(a, i, p, la);
-        hl_str(b, i, p, lb);
+        dev_str(a, i, p, la);
+        dev_str(b, i, p, lb);
         if (la == lb) mine += la;
     }
     for (int m = 32; m >= 1; m >>= 1) mine += __shfl_xor(mine, m, 64);
@@ -56,8 +46,8 @@ __global__ __launch_bounds__(1024) void ham_long_plan_kernel(StrView a, StrView 
         if (i < n) {
             const uint8_t *p;
             uint64_t la, lb;
-            hl_str(a, i, p, la);
-            hl_str(b, i, p, lb);
+            dev_str(a, i, p, la);
+            dev_str(b, i, p, lb);
             c = la == lb && la ? (uint32_t)((la + S - 1) / S) : 1u;
         }
         s[t] = c;
@@ -105,8 +95,8 @@ __global__ __launch_bounds__(256) void ham_long_kernel(HamLongParams P) {
         }
         const uint8_t *pa, *pb;
         uint64_t la, lb;
-        hl_str(P.a, pair, pa, la);
-        hl_str(P.b, pair, pb, lb);
+        dev_str(P.a, pair, pa, la);
+        dev_str(P.b, pair, pb, lb);
         uint32_t cnt = 0;
         const uint64_t at = (uint64_t)sl * S;
         if (la == lb && at < la) {                                 // assert!(len == b.len()): nothing of a mismatched pair is read
@@ -128,8 +118,8 @@ __global__ __launch_bounds__(1024) void ham_long_finish_kernel(HamLongParams P, 
     if (valid) {
         const uint8_t *p;
         uint64_t la, lb;
-        hl_str(P.a, pair, p, la);
-        hl_str(P.b, pair, p, lb);
+        dev_str(P.a, pair, p, la);
+        dev_str(P.b, pair, p, lb);
         same = la == lb;
         const uint32_t s0 = P.start ? P.start[pair] : pair * P.spp, s1 = P.start ? P.start[pair + 1] : s0 + P.spp;
         if (same) {

@@ -7,21 +7,11 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "dev_str.h"
 #include "ham_search_batch_body.h"
 #include "ta_internal.h"
 
 namespace ta {
-
-__device__ __forceinline__ void hb_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
-    if (s.off) {
-        const uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
-        len = o1 - o0;
-    } else {
-        p = s.blob + (uint64_t)i * s.stride;
-        len = s.len;
-    }
-}
 
 template <int NW>
 __global__ __launch_bounds__(256) void ham_search_batch_kernel(HamBatchParams P) {
@@ -30,8 +20,8 @@ __global__ __launch_bounds__(256) void ham_search_batch_kernel(HamBatchParams P)
     const uint32_t pair = P.list ? P.list[idx] : idx;
     const uint8_t *np, *hay;
     uint64_t nl, h;
-    hb_str(P.nd, pair, np, nl);
-    hb_str(P.hs, pair, hay, h);
+    dev_str(P.nd, pair, np, nl);
+    dev_str(P.hs, pair, hay, h);
     P.counts[pair] = ham_batch_pair_regs<NW>(np, nl, hay, h, P.k, P.best != 0, P.matches + (uint64_t)pair * P.cap, P.cap);
 }
 
@@ -41,8 +31,8 @@ __global__ __launch_bounds__(256) void ham_search_batch_mem_kernel(HamBatchParam
     const uint32_t pair = P.list ? P.list[idx] : idx;
     const uint8_t *np, *hay;
     uint64_t nl, h;
-    hb_str(P.nd, pair, np, nl);
-    hb_str(P.hs, pair, hay, h);
+    dev_str(P.nd, pair, np, nl);
+    dev_str(P.hs, pair, hay, h);
     P.counts[pair] = ham_batch_pair_mem(np, nl, hay, h, P.k, P.best != 0, P.matches + (uint64_t)pair * P.cap, P.cap);
 }
 
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(512) void ham_search_batch_bits_kernel(HamBatchPara
     };
     const uint8_t *hay;
     uint64_t h;
-    hb_str(P.hs, pair, hay, h);
+    dev_str(P.hs, pair, hay, h);
     P.counts[pair] = ham_batch_pair_bits<B>(needle, nlen, hay, h, P.k, P.best != 0, lookup, P.matches + (uint64_t)pair * P.cap, P.cap);
 }
 

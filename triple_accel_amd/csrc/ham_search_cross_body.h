@@ -127,12 +127,13 @@ TA_HD inline ta_match hsx_best(uint64_t w, uint32_t needle_len) {
 constexpr uint32_t HSX_STAGE = 64;
 
 // ---- haystacks per workgroup.  The table is built once per workgroup, so a workgroup takes as many haystacks as still leave about 2,048
-// workgroups (lev_search_cross_body.h: sx_plan); forced > 0: a test's value.
-inline uint32_t hsx_hpw(uint64_t nn, uint64_t nh, uint64_t forced) {
-    const uint64_t groups = (nn + SX_GROUP - 1) / SX_GROUP;
+// workgroups (lev_search_cross_body.h: sx_plan), and at least min_hpw: one full step of its eight wavefronts -- SX_WAVES over groups of
+// SX_GROUP needles, 2 SX_WAVES over the two-word route's groups of HSX2_GROUP (two haystacks per wavefront); forced > 0: a test's value.
+inline uint32_t hsx_hpw(uint64_t nn, uint64_t nh, uint64_t forced, uint32_t group_size = SX_GROUP, uint32_t min_hpw = SX_WAVES) {
+    const uint64_t groups = (nn + group_size - 1) / group_size;
     const uint64_t wgs = 2048 / (groups ? groups : 1) + 1;
     uint64_t hpw = forced ? forced : (nh + wgs - 1) / wgs;
-    if (!forced && hpw < SX_WAVES) hpw = SX_WAVES;
+    if (!forced && hpw < min_hpw) hpw = min_hpw;
     if (hpw > nh) hpw = nh;
     return (uint32_t)(hpw ? hpw : 1);
 }

@@ -11,25 +11,16 @@
 // haystacks' bytes c are and however many slots (haystacks) a half holds.  Lanes l and l + 32 share a column but sit in different
 // halves: they never meet.  The build's stores and atomics run once per workgroup.
 // The two-word counters give the exact mismatch count of every window within the threshold, folded into the lane's Best triple on the
-// spot; the stage, its flush, the per-haystack count and the packed word are ham_search_cross_kernel's.
+// spot.  Lane ownership, the walk, the stage, its flush, the per-haystack count and the packed word are search_cross_dev.h's
+// (hsx_walk_emit), shared with ham_search_cross.hip.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "ham_search_cross_w2_body.h"
+#include "search_cross_dev.h"
 #include "ta_internal.h"
 
 namespace ta {
-
-__device__ __forceinline__ void hsx2_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
-    if (s.off) {
-        const uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
-        len = o1 - o0;
-    } else {
-        p = s.blob + (uint64_t)i * s.stride;
-        len = s.len;
-    }
-}
 
 template <int B>
 __global__ __launch_bounds__(512) void ham_search_cross_w2_kernel(HamSearchCrossParams P) {
@@ -37,19 +28,10 @@ __global__ __launch_bounds__(512) void ham_search_cross_w2_kernel(HamSearchCross
     __shared__ ta_search_cross_hit stage[SX_WAVES][HSX_STAGE];                    // 12 KB: 76 KB per workgroup, two workgroups per CU
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t g0 = blockIdx.y * HSX2_GROUP;
-    const uint32_t size = hsx2_group_size(P.nn, blockIdx.y), G = sx_group_cols(size), S = 64u / G;
-    const uint32_t col = lane & (G - 1u), slot = lane / G, column = lane & (HSX2_GROUP - 1u), half = lane >> 5;
-    const bool has_needle = col < size;
-    const uint32_t needle = g0 + col;
-    const uint8_t *np = nullptr;
-    uint32_t n = 0;
-    if (has_needle) {
-        uint64_t nl;
-        hsx2_str(P.nd, needle, np, nl);
-        n = nl < (uint64_t)HSX2_MAX_NEEDLE + 1u ? (uint32_t)nl : HSX2_MAX_NEEDLE + 1u;   // (max_len bounds every needle: 65 in no valid call)
-    }
-    const bool scans = has_needle && hsx2_scans(n);
+    const uint32_t column = lane & (HSX2_GROUP - 1u), half = lane >> 5;
+    const SxLane L = sx_lane(P.nd, P.nn, blockIdx.y, HSX2_GROUP, HSX2_MAX_NEEDLE + 1u);   // (max_len bounds every needle: 65 in no valid call)
+    const uint32_t n = L.n;
+    const bool scans = L.has_needle && hsx2_scans(n);
     // the table: lanes l and l + 32 own one column (the same needle), word l / 32 of it each.  Wavefront w fills rows 32 w .. 32 w + 31
     // with "every position mismatches", then (behind a barrier) needle byte j clears its bit, byte j by half-wavefront j mod 16 -- two
     // bytes of one needle may name the same row: an LDS atomic
@@ -61,7 +43,7 @@ __global__ __launch_bounds__(512) void ham_search_cross_w2_kernel(HamSearchCross
         for (uint32_t j = wave * 2u + half; j < n; j += 2u * SX_WAVES) {
             uint32_t w;
             const uint32_t bit = hsx2_mis_bit(n, j, w);
-            atomicAnd(&mis[hsx2_mis_at((uint32_t)np[j], column, w)], ~bit);
+            atomicAnd(&mis[hsx2_mis_at((uint32_t)L.np[j], column, w)], ~bit);
         }
     __syncthreads();
 
@@ -71,48 +53,9 @@ __global__ __launch_bounds__(512) void ham_search_cross_w2_kernel(HamSearchCross
         const u32x2 v = *(const u32x2 *)((const uint8_t *)mis + a);
         return HamBits2Word{v.x, v.y};
     };
-    auto any = [](bool p) -> bool { return __ballot(p) != 0ull; };
-    // the wavefront's staged records go out: ONE add to the counter for up to 64 records
-    auto flush = [&](uint32_t cnt) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        unsigned long long base = 0;
-        if (lane == 0) base = atomicAdd(P.count, (unsigned long long)cnt);
-        base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) | __builtin_amdgcn_readfirstlane((uint32_t)base);
-        if (lane < cnt && base + lane < P.cap) P.hits[base + lane] = stage[wave][lane];
-        __builtin_amdgcn_wave_barrier();
-    };
-    uint32_t staged = 0;                                                          // records in the wavefront's stage (wavefront-uniform)
-
-    const uint64_t wg0 = (uint64_t)blockIdx.x * P.hpw;                            // the workgroup's haystacks: [wg0, wg1)
-    const uint64_t wg1 = wg0 + P.hpw < P.nh ? wg0 + P.hpw : P.nh;
-    for (uint32_t it = 0;; it++) {
-        if (wg0 + sx_local_hay(it, wave, S, 0) >= wg1) break;                    // (wavefront-uniform: the ballot below sees every lane)
-        const uint64_t hi = wg0 + sx_local_hay(it, wave, S, slot);
-        HsxBest r = {TA_NONE, 0u, 0u, false};
-        bool live = false;                                                       // 1 <= n <= h: the pairs the reference looks at
-        if (scans && hi < wg1) {
-            const uint8_t *hay;
-            uint64_t h;
-            hsx2_str(P.hs, (uint32_t)hi, hay, h);
-            live = (uint64_t)n <= h;
-            if (live) hsx2_scan_pair<B>(hay, (uint32_t)h, lookup, n, P.kc, any, r);
-        }
-        const bool hit = live && !r.nul && r.count != 0u;
-        if (live && r.nul && P.per_haystack) P.per_haystack[hi] = TA_NONE;       // (every lane of the haystack stores the same word)
-        const unsigned long long mask = __ballot(hit);
-        if (!mask) continue;
-        const uint32_t hits_now = (uint32_t)__popcll(mask);
-        if (staged + hits_now > HSX_STAGE) { flush(staged); staged = 0; }          // (wavefront-uniform)
-        if (hit) {
-            stage[wave][staged + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] =
-                ta_search_cross_hit{(uint32_t)hi, needle, r.start, r.start + n, r.d, r.count};
-            if (P.per_haystack) atomicAdd(P.per_haystack + hi, 1u);
-            if (P.packed) atomicMin(P.packed + hi, (unsigned long long)hsx_word(r.d, needle, r.start));
-        }
-        staged += hits_now;
-    }
-    if (staged) flush(staged);
+    hsx_walk_emit(P, L, scans, stage[wave], [&](const uint8_t *hay, uint32_t h, auto any, HsxBest &r) {
+        hsx2_scan_pair<B>(hay, h, lookup, n, P.kc, any, r);
+    });
 }
 
 hipError_t ham_search_cross_w2_launch(const HamSearchCrossParams &P, hipStream_t st) {

@@ -22,13 +22,11 @@ constexpr uint32_t HSX2_MAX_NEEDLE = 64;   // two dwords of positions
 // ---- the planes.  kc = min(k, longest needle) (hsx_threshold) now reaches 64: B = the smallest plane count with 2^B - 1 >= kc, 1..7.
 TA_HD inline int hsx2_planes(uint32_t kc) { return kc <= HSX2_MAX_NEEDLE ? ham_bits2_planes(kc) : 0; }
 
-// ---- the lane mapping.  A group of `size` needles (1..32) takes G = size rounded up to a power of two columns (sx_group_cols); lane l
-// owns needle l mod G of the group and haystack slot l / G: 64 / G >= 2 haystacks per wavefront (sx_local_hay with S = 64 / G).  The
-// table has one column per lane of a 32-lane half: lane l reads column l mod 32, which holds needle (l mod 32) mod G = l mod G.
-TA_HD inline uint32_t hsx2_group_size(uint32_t nn, uint32_t group) {
-    const uint32_t left = nn - group * HSX2_GROUP;
-    return left < HSX2_GROUP ? left : HSX2_GROUP;
-}
+// ---- the lane mapping.  A group of `size` needles (1..32: sx_group_size over HSX2_GROUP) takes G = size rounded up to a power of two
+// columns (sx_group_cols); lane l owns needle l mod G of the group and haystack slot l / G: 64 / G >= 2 haystacks per wavefront
+// (sx_local_hay with S = 64 / G).  The table has one column per lane of a 32-lane half: lane l reads column l mod 32, which holds
+// needle (l mod 32) mod G = l mod G.  (hsx2_group_size: the rule under this route's name, as the host emulation spells it.)
+TA_HD inline uint32_t hsx2_group_size(uint32_t nn, uint32_t group) { return sx_group_size(nn, group, HSX2_GROUP); }
 
 // ---- the table.  Word w of column l of row c = word w of ham_bits2_mis(needle of column l, n, c), at dword hsx2_mis_at(c, l, w): the
 // two words of a column lie side by side, so a lane takes both with one 8-byte read at byte c * 256 + l * 8.  Built as the one-word
@@ -97,15 +95,9 @@ TA_HD inline void hsx2_scan_pair(const uint8_t *hay, uint32_t h, Mis mis, uint32
     r.nul = nul != 0u;
 }
 
-// ---- haystacks per workgroup: hsx_hpw's rule over groups of 32 needles -- a workgroup takes as many haystacks as still leave about
-// 2,048 workgroups, and at least one full step of its eight wavefronts (two haystacks each); forced > 0: a test's value.
-inline uint32_t hsx2_hpw(uint64_t nn, uint64_t nh, uint64_t forced) {
-    const uint64_t groups = (nn + HSX2_GROUP - 1) / HSX2_GROUP;
-    const uint64_t wgs = 2048 / (groups ? groups : 1) + 1;
-    uint64_t hpw = forced ? forced : (nh + wgs - 1) / wgs;
-    if (!forced && hpw < 2u * SX_WAVES) hpw = 2u * SX_WAVES;
-    if (hpw > nh) hpw = nh;
-    return (uint32_t)(hpw ? hpw : 1);
-}
+// ---- haystacks per workgroup: hsx_hpw over groups of HSX2_GROUP needles, at least HSX2_MIN_HPW -- one full step of the eight
+// wavefronts, two haystacks each.
+constexpr uint32_t HSX2_MIN_HPW = 2u * SX_WAVES;
+inline uint32_t hsx2_hpw(uint64_t nn, uint64_t nh, uint64_t forced) { return hsx_hpw(nn, nh, forced, HSX2_GROUP, HSX2_MIN_HPW); }
 
 }  // namespace ta

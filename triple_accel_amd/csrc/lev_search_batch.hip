@@ -6,21 +6,11 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "dev_str.h"
 #include "lev_search_batch_body.h"
 #include "ta_internal.h"
 
 namespace ta {
-
-__device__ __forceinline__ void sb_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
-    if (s.off) {
-        const uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
-        len = o1 - o0;
-    } else {
-        p = s.blob + (uint64_t)i * s.stride;
-        len = s.len;
-    }
-}
 
 // the longest string of each CSR side (max[0] needles, max[1] haystacks; pre-zeroed): 64-bit, a haystack may pass 4 GiB
 __global__ void search_batch_maxlen_kernel(StrView nd, StrView hs, uint32_t n, unsigned long long *max) {
@@ -28,8 +18,8 @@ __global__ void search_batch_maxlen_kernel(StrView nd, StrView hs, uint32_t n, u
     if (i >= n) return;
     const uint8_t *p;
     uint64_t ln = 0, lh = 0;
-    if (nd.off) sb_str(nd, i, p, ln);
-    if (hs.off) sb_str(hs, i, p, lh);
+    if (nd.off) dev_str(nd, i, p, ln);
+    if (hs.off) dev_str(hs, i, p, lh);
     if (ln) atomicMax(&max[0], (unsigned long long)ln);
     if (lh) atomicMax(&max[1], (unsigned long long)lh);
 }
@@ -44,8 +34,8 @@ __global__ __launch_bounds__(256) void lev_search_batch_kernel(SearchBatchParams
     const uint32_t pair = P.list ? P.list[idx] : idx;
     const uint8_t *np, *hay;
     uint64_t nl, h;
-    sb_str(P.nd, pair, np, nl);
-    sb_str(P.hs, pair, hay, h);
+    dev_str(P.nd, pair, np, nl);
+    dev_str(P.hs, pair, hay, h);
     const SearchCosts C{P.k, P.mc, P.gc, P.sg, P.tc, P.anchored};
     SearchBatchSink sink;
     sink.init(P.matches + (uint64_t)pair * P.cap, P.cap, P.best != 0, P.k);
@@ -71,8 +61,8 @@ __global__ __launch_bounds__(256) void lev_search_batch_mem_kernel(SearchBatchPa
         const uint32_t pair = P.list ? P.list[idx] : idx;
         const uint8_t *np, *hay;
         uint64_t nl, h;
-        sb_str(P.nd, pair, np, nl);
-        sb_str(P.hs, pair, hay, h);
+        dev_str(P.nd, pair, np, nl);
+        dev_str(P.hs, pair, hay, h);
         SearchBatchSink sink;
         sink.init(P.matches + (uint64_t)pair * P.cap, P.cap, P.best != 0, P.k);
         const uint32_t n = nl < (uint64_t)P.max_needle ? (uint32_t)nl : P.max_needle;
@@ -113,7 +103,7 @@ __global__ __launch_bounds__(NWF == 1 ? 512 : 256) void lev_search_batch_scan_ke
     if (valid) {
         const uint8_t *hay;
         uint64_t h;
-        sb_str(P.hs, pair, hay, h);
+        dev_str(P.hs, pair, hay, h);
         auto lookup = [&](uint32_t c, int w) -> uint32_t {
             if (NWF == 1) return peq[c * 64u + lane];
             return peq[2u * c + (uint32_t)w];

@@ -7,24 +7,16 @@
 // Exact: one lane per candidate (anchored: per (haystack, needle) of the sub-batch), lev_search_batch_body.h's recurrence over the span
 // with the online Best fold; a hit is counted, appended, folded into its haystack's nearest word and count, and kept in its record.
 // Finish: the record that carries its haystack's nearest word writes best[i].
+// Lane ownership, the walk, the candidate append and the exact kernel's epilogue are search_cross_dev.h's (the epilogue shared with
+// lev_search_cross_w2.hip, the rest with the Hamming panel kernels).
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "lev_search_cross_body.h"
+#include "search_cross_dev.h"
 #include "ta_internal.h"
 
 namespace ta {
-
-__device__ __forceinline__ void sx_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
-    if (s.off) {
-        const uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
-        len = o1 - o0;
-    } else {
-        p = s.blob + (uint64_t)i * s.stride;
-        len = s.len;
-    }
-}
 
 __global__ void search_cross_init_best_kernel(ta_match *best, uint32_t nh) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -35,19 +27,9 @@ template <bool TRANS>
 __global__ __launch_bounds__(512) void lev_search_cross_scan_kernel(SearchCrossParams P) {
     __shared__ __attribute__((aligned(16))) uint32_t peq[256 * SX_GROUP];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t g0 = blockIdx.y * SX_GROUP;
-    const uint32_t size = sx_group_size(P.nn, blockIdx.y), G = sx_group_cols(size), S = SX_GROUP / G;
-    const uint32_t col = lane & (G - 1u), slot = lane / G;
-    const bool has_needle = col < size;
-    const uint32_t needle = g0 + col;
-    const uint8_t *np = nullptr;
-    uint32_t n = 0;
-    if (has_needle) {
-        uint64_t nl;
-        sx_str(P.nd, needle, np, nl);
-        n = nl < (uint64_t)SX_MAX_NEEDLE ? (uint32_t)nl : SX_MAX_NEEDLE;       // (max_len bounds every needle: no clamp in a valid call)
-    }
-    const bool scans = has_needle && sx_scans(n, P.kf);
+    const SxLane L = sx_lane(P.nd, P.nn, blockIdx.y, SX_GROUP, SX_MAX_NEEDLE);
+    const uint32_t n = L.n;
+    const bool scans = L.has_needle && sx_scans(n, P.kf);
     // the table: wavefront w fills rows 32 w .. 32 w + 31 of its lanes' columns with the wildcard word, then (behind a barrier) adds the
     // needles' own bits, needle byte j by wavefront j mod 8 -- two bytes of one needle may name the same row: an LDS atomic
     const uint32_t wild = scans ? sx_peq_wild(n) : 0u;
@@ -55,35 +37,16 @@ __global__ __launch_bounds__(512) void lev_search_cross_scan_kernel(SearchCrossP
     for (uint32_t c = wave * 32u; c < wave * 32u + 32u; c++) peq[c * SX_GROUP + lane] = wild;
     __syncthreads();
     if (scans)
-        for (uint32_t j = wave; j < n; j += SX_WAVES) atomicOr(&peq[(uint32_t)np[j] * SX_GROUP + lane], sx_peq_bit(n, j));
+        for (uint32_t j = wave; j < n; j += SX_WAVES) atomicOr(&peq[(uint32_t)L.np[j] * SX_GROUP + lane], sx_peq_bit(n, j));
     __syncthreads();
 
-    const uint64_t wg0 = (uint64_t)P.h0 + (uint64_t)blockIdx.x * P.hpw;          // the workgroup's haystacks: [wg0, wg1)
-    const uint64_t wg1 = wg0 + P.hpw < P.h1 ? wg0 + P.hpw : P.h1;
-    for (uint32_t it = 0;; it++) {
-        if (wg0 + sx_local_hay(it, wave, S, 0) >= wg1) break;                    // (wavefront-uniform: the ballot below sees every lane)
-        const uint64_t hi = wg0 + sx_local_hay(it, wave, S, slot);
-        const bool valid = has_needle && hi < wg1;
-        uint32_t first = 0, last = 0;
-        if (valid) {
-            const uint8_t *hay;
-            uint64_t h;
-            sx_str(P.hs, (uint32_t)hi, hay, h);
-            sx_scan_pair<TRANS>(hay, h, [&](uint32_t c) -> uint32_t { return peq[c * SX_GROUP + lane]; }, n, P.kf, first, last);
-        }
-        const bool cand = valid && first != 0;
-        const unsigned long long mask = __ballot(cand);
-        if (mask) {
-            const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(P.n_rec, (uint32_t)__popcll(mask));
-            base = (uint32_t)__shfl((int)base, (int)leader);
-            if (cand) P.rec[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = SxRec{(uint32_t)hi, needle, first, last, TA_NONE};
-        }
-    }
+    auto lookup = [&](uint32_t c) -> uint32_t { return peq[c * SX_GROUP + lane]; };
+    sx_scan_walk(P, L, [&](const uint8_t *hay, uint64_t h, uint32_t &first, uint32_t &last) {
+        sx_scan_pair<TRANS>(hay, h, lookup, n, P.kf, first, last);
+    });
 }
 
-// lanes stride over the records in whole wavefronts (the appends below are per wavefront)
+// lanes stride over the records in whole wavefronts (sx_exact_emit's appends are per wavefront)
 template <int N, bool TRANS, bool PACKED>
 __global__ __launch_bounds__(256) void lev_search_cross_exact_kernel(SearchCrossParams P) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -102,26 +65,12 @@ __global__ __launch_bounds__(256) void lev_search_cross_exact_kernel(SearchCross
             else { r.hay = P.h0 + (uint32_t)(idx / P.nn); r.needle = (uint32_t)(idx % P.nn); }
             const uint8_t *np, *hay;
             uint64_t nl, h;
-            sx_str(P.nd, r.needle, np, nl);
-            sx_str(P.hs, r.hay, hay, h);
+            dev_str(P.nd, r.needle, np, nl);
+            dev_str(P.hs, r.hay, hay, h);
             const uint32_t n = nl < (uint64_t)N ? (uint32_t)nl : (uint32_t)N;  // (max_len bounds every needle: no clamp in a valid call)
             n_matches = sx_exact_pair<N, TRANS, PACKED>(hay, h, np, n, C, P.n_rec != nullptr, r.a, r.b, P.halo, m);
         }
-        const bool hit = n_matches != 0;
-        if (live) P.rec[idx] = SxRec{r.hay, r.needle, (uint32_t)m.start, (uint32_t)m.end, hit ? m.k : TA_NONE};
-        const unsigned long long mask = __ballot(hit);
-        if (!mask) continue;
-        const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(P.count, (unsigned long long)__popcll(mask));
-        base = ((unsigned long long)__builtin_amdgcn_readlane((uint32_t)(base >> 32), leader) << 32) |
-               __builtin_amdgcn_readlane((uint32_t)base, leader);
-        const unsigned long long at = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        if (hit) {
-            if (at < P.cap) P.hits[at] = ta_search_cross_hit{r.hay, r.needle, (uint32_t)m.start, (uint32_t)m.end, m.k, n_matches};
-            if (P.nearest) atomicMin(P.nearest + r.hay, (unsigned long long)sx_word(m.k, r.needle));
-            if (P.per_haystack) atomicAdd(P.per_haystack + r.hay, 1u);
-        }
+        sx_exact_emit(P, idx, live, r, m, n_matches);
     }
 }
 

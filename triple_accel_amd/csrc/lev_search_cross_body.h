@@ -27,9 +27,10 @@ struct SxRec {
 
 // ---- the lane mapping.  A group of `size` needles (1..64) takes G = size rounded up to a power of two columns; lane l owns needle
 // l mod G of the group and haystack slot l / G: 64 / G haystacks per wavefront.  A column without a needle (l mod G >= size) idles.
-TA_HD inline uint32_t sx_group_size(uint32_t nn, uint32_t group) {
-    const uint32_t left = nn - group * SX_GROUP;
-    return left < SX_GROUP ? left : SX_GROUP;
+// group_size: the needles of a full group (SX_GROUP; the two-word routes' SX2_GROUP and HSX2_GROUP are 32: size 1..32, 64 / G >= 2).
+TA_HD inline uint32_t sx_group_size(uint32_t nn, uint32_t group, uint32_t group_size = SX_GROUP) {
+    const uint32_t left = nn - group * group_size;
+    return left < group_size ? left : group_size;
 }
 TA_HD inline uint32_t sx_group_cols(uint32_t size) {
     uint32_t g = 1;

@@ -11,33 +11,25 @@
 // The build's stores (ds_write_b32 banks modulo 32: word w of columns j and j + 16 meet, 2-way) run once per workgroup.
 // Exact: one lane per candidate (anchored: per (haystack, needle) of the sub-batch), the recurrence with its DP column in HBM scratch
 // (lev_search_tile_mem, element-major over the resident lanes: a wavefront's accesses coalesce) over the span with the online Best
-// fold; the epilogue is lev_search_cross_exact_kernel's.
+// fold; its epilogue is search_cross_dev.h's sx_exact_emit, shared with lev_search_cross.hip.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
 #include "lev_search_cross_w2_body.h"
+#include "search_cross_dev.h"
 #include "ta_internal.h"
 
 namespace ta {
-
-__device__ __forceinline__ void sx2_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
-    if (s.off) {
-        const uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
-        len = o1 - o0;
-    } else {
-        p = s.blob + (uint64_t)i * s.stride;
-        len = s.len;
-    }
-}
 
 template <bool TRANS>
 __global__ __launch_bounds__(512) void lev_search_cross_w2_scan_kernel(SearchCrossParams P) {
     __shared__ __attribute__((aligned(16))) uint32_t peq[256 * SX2_GROUP * 2];
     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    // (lane ownership, the walk and the append are written out here and not taken from search_cross_dev.h's sx_lane and sx_scan_walk:
+    // with them this kernel alone measured 0.5 % and 1.5 % slower on the 12 x 34 and 96 x 40 panels -- profiles/r16)
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t g0 = blockIdx.y * SX2_GROUP;
-    const uint32_t size = sx2_group_size(P.nn, blockIdx.y), G = sx_group_cols(size), S = 64u / G;
+    const uint32_t size = sx_group_size(P.nn, blockIdx.y, SX2_GROUP), G = sx_group_cols(size), S = 64u / G;
     const uint32_t col = lane & (G - 1u), slot = lane / G, column = lane & (SX2_GROUP - 1u), half = lane >> 5;
     const bool has_needle = col < size;
     const uint32_t needle = g0 + col;
@@ -45,7 +37,7 @@ __global__ __launch_bounds__(512) void lev_search_cross_w2_scan_kernel(SearchCro
     uint32_t n = 0;
     if (has_needle) {
         uint64_t nl;
-        sx2_str(P.nd, needle, np, nl);
+        dev_str(P.nd, needle, np, nl);
         n = nl < (uint64_t)SX2_MAX_NEEDLE ? (uint32_t)nl : SX2_MAX_NEEDLE;     // (max_len bounds every needle: no clamp in a valid call)
     }
     const bool scans = has_needle && sx_scans(n, P.kf);
@@ -74,7 +66,7 @@ __global__ __launch_bounds__(512) void lev_search_cross_w2_scan_kernel(SearchCro
         if (valid) {
             const uint8_t *hay;
             uint64_t h;
-            sx2_str(P.hs, (uint32_t)hi, hay, h);
+            dev_str(P.hs, (uint32_t)hi, hay, h);
             sx2_scan_pair<TRANS>(hay, h, [&](uint32_t c, uint32_t (&Eq)[2]) {
                 const u32x2 v = *(const u32x2 *)&peq[sx2_peq_at(c, column, 0)];
                 Eq[0] = v.x; Eq[1] = v.y;
@@ -92,8 +84,8 @@ __global__ __launch_bounds__(512) void lev_search_cross_w2_scan_kernel(SearchCro
     }
 }
 
-// a persistent grid of P.col_lanes lanes, one memory-backed column each; the lanes stride over the records in whole wavefronts (the
-// appends below are per wavefront).  TRANS: the costs have a transposition term (P.tc is its cost)
+// a persistent grid of P.col_lanes lanes, one memory-backed column each; the lanes stride over the records in whole wavefronts
+// (sx_exact_emit's appends are per wavefront).  TRANS: the costs have a transposition term (P.tc is its cost)
 template <bool TRANS>
 __global__ __launch_bounds__(256) void lev_search_cross_w2_exact_kernel(SearchCrossParams P) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -113,26 +105,12 @@ __global__ __launch_bounds__(256) void lev_search_cross_w2_exact_kernel(SearchCr
             else { r.hay = P.h0 + (uint32_t)(idx / P.nn); r.needle = (uint32_t)(idx % P.nn); }
             const uint8_t *np, *hay;
             uint64_t nl, h;
-            sx2_str(P.nd, r.needle, np, nl);
-            sx2_str(P.hs, r.hay, hay, h);
+            dev_str(P.nd, r.needle, np, nl);
+            dev_str(P.hs, r.hay, hay, h);
             const uint32_t n = nl < (uint64_t)SX2_MAX_NEEDLE ? (uint32_t)nl : SX2_MAX_NEEDLE;   // (the column has room for 64 rows)
             n_matches = sx2_exact_pair<TRANS>(hay, h, np, n, C, P.n_rec != nullptr, r.a, r.b, P.halo, col, lanes, m);
         }
-        const bool hit = n_matches != 0;
-        if (live) P.rec[idx] = SxRec{r.hay, r.needle, (uint32_t)m.start, (uint32_t)m.end, hit ? m.k : TA_NONE};
-        const unsigned long long mask = __ballot(hit);
-        if (!mask) continue;
-        const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-        unsigned long long base = 0;
-        if (lane == leader) base = atomicAdd(P.count, (unsigned long long)__popcll(mask));
-        base = ((unsigned long long)__builtin_amdgcn_readlane((uint32_t)(base >> 32), leader) << 32) |
-               __builtin_amdgcn_readlane((uint32_t)base, leader);
-        const unsigned long long at = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        if (hit) {
-            if (at < P.cap) P.hits[at] = ta_search_cross_hit{r.hay, r.needle, (uint32_t)m.start, (uint32_t)m.end, m.k, n_matches};
-            if (P.nearest) atomicMin(P.nearest + r.hay, (unsigned long long)sx_word(m.k, r.needle));
-            if (P.per_haystack) atomicAdd(P.per_haystack + r.hay, 1u);
-        }
+        sx_exact_emit(P, idx, live, r, m, n_matches);
     }
 }
 

@@ -21,13 +21,11 @@ constexpr uint32_t SX2_COL_WORDS = 6u * (SX2_MAX_NEEDLE + 1u);   // one lane's m
 // the exact pass's resident lanes: their columns stay within SX_BUDGET (172,032 lanes of 1,560 bytes)
 constexpr uint64_t SX2_MAX_LANES = SX_BUDGET / (SX2_COL_WORDS * 4u) / 256u * 256u;
 
-// ---- the lane mapping.  A group of `size` needles (1..32) takes G = size rounded up to a power of two columns (sx_group_cols); lane l
-// owns needle l mod G of the group and haystack slot l / G: 64 / G >= 2 haystacks per wavefront (sx_local_hay with S = 64 / G).  The
-// table has one column per lane of a 32-lane half: lane l reads column l mod 32, which holds needle (l mod 32) mod G = l mod G.
-TA_HD inline uint32_t sx2_group_size(uint32_t nn, uint32_t group) {
-    const uint32_t left = nn - group * SX2_GROUP;
-    return left < SX2_GROUP ? left : SX2_GROUP;
-}
+// ---- the lane mapping.  A group of `size` needles (1..32: sx_group_size over SX2_GROUP) takes G = size rounded up to a power of two
+// columns (sx_group_cols); lane l owns needle l mod G of the group and haystack slot l / G: 64 / G >= 2 haystacks per wavefront
+// (sx_local_hay with S = 64 / G).  The table has one column per lane of a 32-lane half: lane l reads column l mod 32, which holds
+// needle (l mod 32) mod G = l mod G.  (sx2_group_size: the rule under this route's name, as the host emulation spells it.)
+TA_HD inline uint32_t sx2_group_size(uint32_t nn, uint32_t group) { return sx_group_size(nn, group, SX2_GROUP); }
 
 // ---- the table.  Word w of column l of row c = lev_filter_peq_word(needle of column l, n, 2, c, w), at dword sx2_peq_at(c, l, w): the
 // two words of a column lie side by side, so a lane takes both with one 8-byte read.  Built as the one-word table: the wildcard words in

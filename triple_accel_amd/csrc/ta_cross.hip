@@ -321,7 +321,7 @@ static int ham_search_cross_run(const ta_strings *needles, size_t nn, const ta_s
     // two-word one for the whole panel (ham_search_cross_w2.hip) -- groups of 32 needles, two haystacks or more per wavefront step
     const bool w2 = max_n > SX_MAX_NEEDLE;
     const int forced = env_int("TA_HSEARCH_CROSS_HPW");
-    P.hpw = w2 ? hsx2_hpw(nn, nh, forced > 0 ? (uint64_t)forced : 0) : hsx_hpw(nn, nh, forced > 0 ? (uint64_t)forced : 0);
+    P.hpw = hsx_hpw(nn, nh, forced > 0 ? (uint64_t)forced : 0, w2 ? HSX2_GROUP : SX_GROUP, w2 ? HSX2_MIN_HPW : SX_WAVES);
     // (names the kernel: ham_search_cross_kernel<B> / ham_search_cross_w2_kernel<B>)
     TA_HIP(w2 ? ham_search_cross_w2_launch(P, st) : ham_search_cross_launch(P, st));
     TA_HIP(ham_search_cross_finish_launch(P, st));

@@ -411,7 +411,8 @@ struct HamCrossParams {
 hipError_t ham_cross_launch(const HamCrossParams &P, int nw, hipStream_t st);
 
 // ta_levenshtein_search_cross and ta_levenshtein_search_cross_with_opts (lev_search_cross.hip; needles beyond 32 bytes:
-// lev_search_cross_w2.hip): every needle of a panel in every haystack, one sub-batch of haystacks per launch
+// lev_search_cross_w2.hip; what the kernels of both share: search_cross_dev.h): every needle of a panel in every haystack, one
+// sub-batch of haystacks per launch
 struct SxRec;
 struct SearchCrossParams {
     StrView nd, hs;               // needles (every one at most 32 bytes; the two-word route: 64), haystacks
@@ -439,8 +440,8 @@ hipError_t search_cross_finish_launch(const SearchCrossParams &P, hipStream_t st
 hipError_t search_cross_w2_scan_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
 hipError_t search_cross_w2_exact_launch(const SearchCrossParams &P, bool trans, hipStream_t st);
 
-// ta_hamming_search_cross and ta_hamming_search_cross_with_opts (ham_search_cross.hip; needles beyond 32 bytes: ham_search_cross_w2.hip):
-// every needle of a panel in every haystack, substitutions only, in one launch
+// ta_hamming_search_cross and ta_hamming_search_cross_with_opts (ham_search_cross.hip; needles beyond 32 bytes: ham_search_cross_w2.hip;
+// what the two kernels share: search_cross_dev.h): every needle of a panel in every haystack, substitutions only, in one launch
 struct HamSearchCrossParams {
     StrView nd, hs;               // needles (every one at most 32 bytes; the two-word route: 64), haystacks
     uint32_t nn, nh;

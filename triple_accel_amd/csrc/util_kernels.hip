@@ -1,20 +1,10 @@
 // util_kernels.hip -- Hamming batch kernel (HBM-bound) and the small helper kernels of the batch API.
 #include <hip/hip_runtime.h>
 
+#include "dev_str.h"
 #include "ta_internal.h"
 
 namespace ta {
-
-__device__ __forceinline__ void dev_str(const StrView &s, uint32_t i, const uint8_t *&p, uint64_t &len) {
-    if (s.off) {
-        uint64_t o0 = s.off[i], o1 = s.off[i + 1];
-        p = s.blob + o0;
-        len = o1 - o0;
-    } else {
-        p = s.blob + (uint64_t)i * s.stride;
-        len = s.len;
-    }
-}
 
 // number of nonzero bytes in x (a ^ b): the mismatches of 4 positions
 __device__ __forceinline__ uint32_t nz_bytes(uint32_t x) {
