@@ -477,6 +477,75 @@ def test_hamming_search_phase_form_every_length(monkeypatch):
     assert {"hamming_search_phase_kernel<%d,%d>" % (q, b) for q, b in ((1, 5), (1, 1), (2, 4), (2, 2), (4, 1), (4, 2))} <= used, used
 
 
+def loader_edge_cases():
+    """(family, needle, k, haystack, want) for test_line_ahead_loader_edges.  "ham": haystacks of n, n + 1 and 127..129, 255..257, 511..513
+    bytes, near-copies of the needle at both ends and ending on and just behind every multiple of 128.  "lev": lengths around the last
+    64-column block and 128-byte line behind 4096, a copy across the last block boundary it fits in front of the copy at the very end."""
+    g = Dg.rng(0x11AE)
+    for n, k in ((12, 3), (8, 2)):
+        needle = bytes(int(c) or 1 for c in Dg.random_bytes(g, n))
+        nd = np.frombuffer(needle, dtype=np.uint8)
+        for h in sorted({n, n + 1, 127, 128, 129, 255, 256, 257, 511, 512, 513}):
+            hay = Dg.random_bytes(g, h)
+            hay[hay == 0] = 1
+            inner = [e - n for m in range(128, h, 128) for e in (m, m + 1) if e - n >= 0]
+            for pos in inner + [0, h - n]:                                     # (the two at the ends last, and always within k)
+                hay[pos:pos + n] = nd
+                for q in g.integers(0, n, size=int(g.integers(0, k + 2 if pos in inner else k + 1))):
+                    hay[pos + int(q)] = 7
+            yield "ham", needle, k, hay, O.hamming_search_naive_with_opts(needle, hay.tobytes(), k, O.ALL)
+    for n, k in ((8, 1), (40, 2)):
+        needle = Dg.rand_str(g, n)
+        for h in (4096, 4097, 4159, 4160, 4161, 4223, 4224, 4225):
+            hay = bytearray(g.integers(33, 127, size=h, dtype=np.uint8).tobytes())
+            bnd = (h - 2 * n + n // 2) // 64 * 64
+            for pos in (bnd - n // 2, h - n):
+                hay[pos:pos + n] = needle
+            want = sorted(O.levenshtein_search_naive_with_opts(needle, bytes(hay), k, O.ALL, (1, 1, 0, None), False), key=lambda m: m[1])
+            assert any(m[1] == h for m in want) and any(m[0] < bnd < m[1] for m in want), (n, h)
+            yield "lev", needle, k, bytes(hay), want
+
+
+def test_line_ahead_loader_edges(monkeypatch):
+    """The haystack loader of the lane-per-tile kernels (hay_line.h: one line primed, the next requested under the `< end` guard) at the
+    lengths where a guard can go wrong.  Hamming forms: a lane's tile is at least 256 bytes in lines of 128 (shift-add: 64), so the
+    haystacks of loader_edge_cases end on, just before and just behind a line and a lane; all five forms, each by name; a NUL byte at
+    either end and on a line start is the SIMD contract's panic in the three forms that scan for it.  Levenshtein filter (needs 4096
+    bytes; needles of up to 32 bytes: lev_filter_kernel, two blocks per line; beyond: lev_filter_kernel_n): All-mode hits against the oracle."""
+    import triple_accel_amd as T
+    from triple_accel_amd import batch as B
+    forms = {12: [(None, "hamming_search_phase_kernel<1,2>"), ("TA_HAMMING_SEARCH_NO_PHASE", "hamming_search_bits_kernel<2>")],
+             8: [(None, "hamming_search_swar16_kernel<2>"), ("TA_HAMMING_SEARCH_SA", "hamming_search_sa_kernel<2>"),
+                 ("TA_HAMMING_SEARCH_SWAR", "hamming_search_kernel")]}
+    hits = 0
+    for family, needle, k, hay, want in loader_edge_cases():
+        n, h = len(needle), len(hay)
+        dev = B.haystack_tensor(hay)
+        if family == "lev":
+            got = [tuple(int(v) for v in r) for r in B.levenshtein_search_dev(needle, dev, k)]
+            assert T.last_kernel_name() == ("lev_filter_kernel" if n <= 32 else "lev_filter_kernel_n"), (n, h, T.last_kernel_name())
+            assert got == want, (n, k, h)
+            continue
+        hits += len(want)
+        for sw, kern in forms[n]:
+            if sw:
+                monkeypatch.setenv(sw, "1")
+            got = [tuple(int(v) for v in r) for r in B.hamming_search_dev(needle, dev, k)]
+            name = T.last_kernel_name()
+            if sw in (None, "TA_HAMMING_SEARCH_NO_PHASE"):                 # the forms with the fused NUL scan
+                for zpos in [0, h - 1] + [m for m in (128, 384) if m < h]:
+                    hz = hay.copy()
+                    hz[zpos] = 0
+                    with pytest.raises(T.PanicError):
+                        B.hamming_search_dev(needle, B.haystack_tensor(hz), k)
+                    assert T.last_kernel_name() == kern, (h, zpos, sw)
+            if sw:
+                monkeypatch.delenv(sw)
+            assert name == kern, (n, k, h, sw, name)
+            assert got == want, (n, k, h, sw)
+    assert hits >= 50
+
+
 WEIGHTED = [(2, 2, 0, None), (2, 3, 1, None), (2, 2, 1, 3), (3, 1, 0, None), (1, 2, 0, None), (4, 3, 3, 5), (2, 2, 0, 2), (3, 2, 0, 1)]
 
 

@@ -9,6 +9,7 @@
 
 #include "dev_str.h"
 #include "ham_search_batch_body.h"
+#include "lds_tab64.h"
 #include "ta_internal.h"
 
 namespace ta {
@@ -36,30 +37,19 @@ __global__ __launch_bounds__(256) void ham_search_batch_mem_kernel(HamBatchParam
     P.counts[pair] = ham_batch_pair_mem(np, nl, hay, h, P.k, P.best != 0, P.matches + (uint64_t)pair * P.cap, P.cap);
 }
 
-// Shared needle: Mis[c] kept 64 times (hamming_search_bits_kernel's layout: lane l reads dword l of row c, so no two lanes of a 32-lane
-// group share a bank whatever the bytes are) -- 64 KB, 512 threads, two workgroups per CU.  The lookup's address is one v_perm of the
-// haystack dword: byte b << 8 | lane * 4.
+// Shared needle: Mis[c] kept once per lane of a wavefront (lds_tab64.h) -- 64 KB, 512 threads, two workgroups per CU.
 template <int B>
 __global__ __launch_bounds__(512) void ham_search_batch_bits_kernel(HamBatchParams P) {
     __shared__ __attribute__((aligned(16))) uint32_t mis[256 * 64];
     const uint8_t *needle = P.nd.blob;
     const uint32_t nlen = P.max_needle;
-    {
-        const uint32_t m = ham_bits_mis(needle, nlen, threadIdx.x >> 1);
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 *row = (u32x4 *)(mis + (threadIdx.x >> 1) * 64 + (threadIdx.x & 1u) * 32);
-#pragma unroll
-        for (int q = 0; q < 8; q++) row[q] = u32x4{m, m, m, m};
-    }
+    tab64_fill(mis, ham_bits_mis(needle, nlen, threadIdx.x >> 1));
     __syncthreads();
     const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= P.n) return;
     const uint32_t pair = P.list ? P.list[idx] : idx;
     const uint32_t lane_off = (threadIdx.x & 63u) * 4u;
-    auto lookup = [&](uint32_t v, int b) -> uint32_t {
-        const uint32_t a = __builtin_amdgcn_perm(v, lane_off, 0x0C0C0000u | ((4u + (uint32_t)b) << 8));
-        return *(const uint32_t *)((const uint8_t *)mis + a);
-    };
+    auto lookup = [&](uint32_t v, int b) -> uint32_t { return tab64_lookup(mis, lane_off, v, b); };
     const uint8_t *hay;
     uint64_t h;
     dev_str(P.hs, pair, hay, h);

@@ -8,7 +8,7 @@
 //     S = (S << 8) + T[c]          T[c].byte[j] = (needle[j] != c)
 // i.e. NWS v_alignbyte + NWS v_add (counters never exceed 32, so no carry crosses a byte), with T -- 256 x NWS
 // dwords -- in LDS; counter n-1 is the finished count of offset i-n+1.  ~20 instructions per haystack byte for a
-// 32-byte needle, where the SWAR compare-and-popcount kernel (any needle length, lev_search.hip) needs ~54.
+// 32-byte needle, where the SWAR compare-and-popcount kernel (any needle length, ham_search.hip) needs ~54.
 // Plain per-lane code: tests run the same function on the CPU.
 #pragma once
 #include <stdint.h>

@@ -14,6 +14,7 @@
 #include <stddef.h>
 
 #include "ham_search_cross_body.h"
+#include "lds_tab64.h"
 #include "search_cross_dev.h"
 #include "ta_internal.h"
 
@@ -38,10 +39,7 @@ __global__ __launch_bounds__(512) void ham_search_cross_kernel(HamSearchCrossPar
     __syncthreads();
 
     const uint32_t lane_off = lane * 4u;
-    auto lookup = [&](uint32_t w, int b) -> uint32_t {                            // byte b of w << 8 | lane * 4
-        const uint32_t a = __builtin_amdgcn_perm(w, lane_off, 0x0C0C0000u | ((4u + (uint32_t)b) << 8));
-        return *(const uint32_t *)((const uint8_t *)mis + a);
-    };
+    auto lookup = [&](uint32_t w, int b) -> uint32_t { return tab64_lookup(mis, lane_off, w, b); };
     hsx_walk_emit(P, L, scans, stage[wave], [&](const uint8_t *hay, uint32_t h, auto any, HsxBest &r) {
         hsx_scan_pair<B>(hay, h, lookup, n, P.kc, any, r);
     });

@@ -17,6 +17,7 @@
 #include <stddef.h>
 
 #include "ham_search_cross_w2_body.h"
+#include "lds_tab64.h"
 #include "search_cross_dev.h"
 #include "ta_internal.h"
 
@@ -48,9 +49,8 @@ __global__ __launch_bounds__(512) void ham_search_cross_w2_kernel(HamSearchCross
     __syncthreads();
 
     const uint32_t lane_off = column * 8u;
-    auto lookup = [&](uint32_t w, int b) -> HamBits2Word {                        // byte b of w << 8 | column * 8
-        const uint32_t a = __builtin_amdgcn_perm(w, lane_off, 0x0C0C0000u | ((4u + (uint32_t)b) << 8));
-        const u32x2 v = *(const u32x2 *)((const uint8_t *)mis + a);
+    auto lookup = [&](uint32_t w, int b) -> HamBits2Word {                        // both words of the column: one ds_read_b64
+        const u32x2 v = tab64_lookup<u32x2>(mis, lane_off, w, b);
         return HamBits2Word{v.x, v.y};
     };
     hsx_walk_emit(P, L, scans, stage[wave], [&](const uint8_t *hay, uint32_t h, auto any, HsxBest &r) {

@@ -21,7 +21,7 @@ namespace ta {
 
 constexpr uint32_t FILTER_BLOCK = 64;   // end positions per candidate block
 
-// peq[c] for all 256 byte values (device: built in LDS by the block, see lev_search.hip)
+// peq[c] for all 256 byte values (device: built in LDS by the block, see lev_search.hip and lds_tab64.h)
 TA_HD inline uint32_t lev_filter_peq(const uint8_t *needle, uint32_t n, uint32_t c) {
     uint32_t m = n < 32 ? ((1u << (32 - n)) - 1u) : 0u;            // wildcard rows
     for (uint32_t j = 0; j < n; j++)

@@ -1,12 +1,10 @@
-// lev_search.hip -- gfx950 kernels for levenshtein_search / hamming_search over a haystack shard in HBM.
+// lev_search.hip -- gfx950 kernels for levenshtein_search over a haystack shard in HBM.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdlib.h>
 
-#include "ham_search_body.h"
-#include "ham_swar_body.h"
-#include "ham_bits_body.h"
-#include "ham_phase_body.h"
+#include "hay_line.h"
+#include "lds_tab64.h"
 #include "lev_filter_body.h"
 #include "lev_search_body.h"
 #include "lev_search_wave_body.h"
@@ -100,31 +98,18 @@ hipError_t lev_search_launch(const SearchParams &P, bool packed, bool trans, hip
 // One lane scans P.tile end positions (a multiple of 64) after P.halo bytes of left context and appends the index of
 // every 64-column block that holds a cost <= k to `list` (lev_filter_body.h).  The 256-entry match table of the
 // needle lives in LDS; the haystack is read 16 bytes per lane per load.
-// REPL: the match table is kept 64 times -- row c (256 bytes) holds peq[c] once per lane of a wavefront, lane l reads dword l of
-// the row -- so the 64 lookups of a wavefront fall on 64 different addresses of which no two in a 32-lane group share a bank
-// (ds_read_b32: bank = dword index mod 32), whatever the haystack bytes are; one flat 256-entry table indexed by a random byte
-// per lane costs ~4.3 extra LDS cycles per lookup (SQ_LDS_BANK_CONFLICT 72.6 M per GiB, profiles/r02).  The address is built
-// by ONE v_perm_b32 per byte -- [lane*4 | c << 8] -- where the flat table needs one SDWA shift: the VALU count is unchanged.
+// REPL: the match table is kept once per lane of a wavefront (lds_tab64.h: 512 threads, two workgroups = 16 wavefronts per CU);
+// without it (TA_FILTER_FLAT=1) one flat 256-entry table, bank conflicts on random bytes.
 template <bool TRANS, bool REPL, bool EXACT = false>
 __global__ __launch_bounds__(REPL ? 512 : 256) void lev_filter_kernel(SearchParams P, uint32_t *list, uint32_t list_cap, unsigned int *list_count) {
     __shared__ __attribute__((aligned(16))) uint32_t peq[REPL ? 256 * 64 : 256];
-    if (REPL) {                                    // 512 threads: two per row, half a row each (two workgroups = 16 wavefronts per CU)
-        const uint32_t m = lev_filter_peq(P.needle, P.needle_len, threadIdx.x >> 1);
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 *row = (u32x4 *)(peq + (threadIdx.x >> 1) * 64 + (threadIdx.x & 1u) * 32);
-#pragma unroll
-        for (int q = 0; q < 8; q++) row[q] = u32x4{m, m, m, m};
-    } else {
-        peq[threadIdx.x] = lev_filter_peq(P.needle, P.needle_len, threadIdx.x);
-    }
+    if (REPL) tab64_fill(peq, lev_filter_peq(P.needle, P.needle_len, threadIdx.x >> 1));
+    else peq[threadIdx.x] = lev_filter_peq(P.needle, P.needle_len, threadIdx.x);
     __syncthreads();
     const uint32_t lane_off = (threadIdx.x & 63u) * 4u;
     // table entry of byte b (0..3) of dword v
     auto lookup = [&](uint32_t v, int b) -> uint32_t {
-        if (REPL) {
-            const uint32_t a = __builtin_amdgcn_perm(v, lane_off, 0x0C0C0000u | ((4u + (uint32_t)b) << 8));   // lane*4 | byte b << 8
-            return *(const uint32_t *)((const uint8_t *)peq + a);
-        }
+        if (REPL) return tab64_lookup(peq, lane_off, v, b);
         return peq[(v >> (8 * b)) & 0xffu];
     };
     const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -142,23 +127,13 @@ __global__ __launch_bounds__(REPL ? 512 : 256) void lev_filter_kernel(SearchPara
         const unsigned int idx = atomicAdd(list_count, 1u);
         if (idx < list_cap) list[idx] = (uint32_t)(col / FILTER_BLOCK);
     };
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
     uint64_t i = emit_begin;
     const uint64_t full_end = emit_begin + ((emit_end - emit_begin) & ~(uint64_t)(FILTER_BLOCK - 1));
-    // a whole 128-byte LINE per lane is requested at once (eight 16-byte loads in one burst, tiles start on 128-byte
-    // multiples), one line ahead: every line of the haystack crosses the L2's fabric side once (two 64-byte bursts 64 columns
-    // apart measured 1.31x: the second half had left the 4 MB L2 by the time its lane came back for it)
-    constexpr uint32_t LINE = 2 * FILTER_BLOCK;
-    u32x4u nxt[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) nxt[q] = (i + 16u * q < emit_end) ? *(const u32x4u *)(hay + i + 16u * q) : u32x4u{0, 0, 0, 0};
+    static_assert(2 * FILTER_BLOCK == 128, "a line of eight quads is two blocks");
+    u32x4u nxt[8], cur[8];
+    hay_line_prime<8>(nxt, hay, i, emit_end);                     // a whole 128-byte line per lane, one line ahead (hay_line.h)
     while (i < full_end) {                                        // whole 64-column blocks, two per line
-        u32x4u cur[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) cur[q] = nxt[q];
-#pragma unroll
-        for (int q = 0; q < 8; q++)                               // blobs carry 16 bytes of slack
-            if (i + LINE + 16u * q < emit_end) nxt[q] = *(const u32x4u *)(hay + i + LINE + 16u * q);
+        hay_line_turn<8>(cur, nxt, hay, i, emit_end);
 #pragma unroll 1
         for (int blk = 0; blk < 2 && i < full_end; blk++) {
             bool any = false;
@@ -220,19 +195,12 @@ __global__ __launch_bounds__(256) void lev_filter_kernel_n(SearchParams P, uint3
         if (idx < list_cap) list[idx] = (uint32_t)(col / FILTER_BLOCK);
     };
     for (uint64_t i = col_begin; i < emit_begin; i++) stepc(hay[i]);               // left context
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
     uint64_t i = emit_begin;
     const uint64_t full_end = emit_begin + ((emit_end - emit_begin) & ~(uint64_t)(FILTER_BLOCK - 1));
-    u32x4u nxt[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) nxt[q] = (i + 16u * q < emit_end) ? *(const u32x4u *)(hay + i + 16u * q) : u32x4u{0, 0, 0, 0};
+    u32x4u nxt[4], cur[4];
+    hay_line_prime<4>(nxt, hay, i, emit_end);
     while (i < full_end) {                                        // whole 64-column blocks, requested one block ahead
-        u32x4u cur[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) cur[q] = nxt[q];
-#pragma unroll
-        for (int q = 0; q < 4; q++)                               // blobs carry 16 bytes of slack
-            if (i + FILTER_BLOCK + 16u * q < emit_end) nxt[q] = *(const u32x4u *)(hay + i + FILTER_BLOCK + 16u * q);
+        hay_line_turn<4>(cur, nxt, hay, i, emit_end);
         bool any = false;
 #pragma unroll 1
         for (int q = 0; q < 4; q++) {
@@ -501,520 +469,6 @@ hipError_t lev_search_list_launch(const SearchParams &P, bool /*trans*/, const u
     if (n_list == 0) return hipSuccess;
     if (P.needle_len <= 32) return hipErrorInvalidValue;
     hipLaunchKernelGGL(lev_search_mem_list_kernel, dim3((n_list + 63) / 64), dim3(64), 0, s, P, list, n_list);
-    return hipGetLastError();
-}
-
-// hamming_search: one lane per aligned group of 4 consecutive haystack offsets.  The lane loads the aligned dwords
-// covering its 4 windows once (coalesced), re-aligns them per offset with v_alignbyte, and counts non-zero bytes of
-// window ^ needle with the SWAR test + v_bcnt accumulate.  Replaces hamming_search_simd_core_*
-// (src/hamming.rs:481-552); contract: mismatches(offset) <= k for every offset 0..=h-n.
-__global__ __launch_bounds__(256) void hamming_search_kernel(SearchParams P, uint32_t delta) {
-    const uint64_t grp = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;   // aligned dword index of the group's first byte
-    const uint32_t n = P.needle_len;
-    const uint64_t h = P.hay_len;
-    const uint64_t last = h - n;                                            // last valid offset
-    const uint64_t byte0 = grp * 4;                                         // in the aligned-down address space
-    if (byte0 > last + delta) return;
-    const uint32_t *hw = (const uint32_t *)(P.hay - delta) + grp;
-    const uint32_t nwords = (n + 3) >> 2;
-    const uint32_t tail_mask = (n & 3) ? (0xFFFFFFFFu >> (8 * (4 - (n & 3)))) : 0xFFFFFFFFu;
-    uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    uint32_t lo = hw[0];
-    for (uint32_t w = 0; w < nwords; w++) {
-        const uint32_t hi = hw[w + 1];
-        uint32_t nd;                                                        // needle word w (wave-uniform)
-        {
-            typedef uint32_t u32u __attribute__((aligned(1)));
-            nd = *(const u32u *)(P.needle_dev + 4 * w);                     // needle_dev carries 16 bytes of slack
-        }
-        // byte test with one v_perm_b32 (wave.h ne12): the needle word carries ^ 0x0C, a window byte then XORs to 12 exactly
-        // where it matches; bytes past the needle's end are forced to 12.  Every mismatching byte adds 8 one-bits.
-        const uint32_t m = (w + 1 == nwords) ? tail_mask : 0xFFFFFFFFu;
-        const uint32_t nd12 = nd ^ 0x0C0C0C0Cu, pad = 0x0C0C0C0Cu & ~m;
-        auto nz = [&](uint32_t win) -> uint32_t {
-            return __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, ((win ^ nd12) & m) | pad);
-        };
-        c0 += __builtin_popcount(nz(lo));
-        c1 += __builtin_popcount(nz(__builtin_amdgcn_alignbyte(hi, lo, 1)));
-        c2 += __builtin_popcount(nz(__builtin_amdgcn_alignbyte(hi, lo, 2)));
-        c3 += __builtin_popcount(nz(__builtin_amdgcn_alignbyte(hi, lo, 3)));
-        lo = hi;
-    }
-    const uint32_t cnt[4] = {c0 >> 3, c1 >> 3, c2 >> 3, c3 >> 3};
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const uint64_t b = byte0 + r;
-        if (b < delta) continue;
-        const uint64_t pos = b - delta;
-        if (pos > last) continue;
-        if (cnt[r] <= P.k) {
-            unsigned long long idx = atomicAdd(P.count, 1ull);
-            if (idx < P.cap) P.hits[idx] = ta_match{P.base + pos, P.base + pos + n, cnt[r], 0u};
-        }
-    }
-}
-
-// needles of up to 64 bytes, SWAR form (ham_swar_body.h): one lane per 16 consecutive offsets, three 16-byte loads per lane in flight
-// together, the windows of a lane shifted once and shared by its offsets.  The NUL-byte scan of the SIMD contract (src/lib.rs:237-243)
-// rides along: every haystack dword is the first of exactly one lane's four.  delta = hay & 15 (the loads are 16-byte aligned).
-template <int NW>
-__global__ __launch_bounds__(256) void hamming_search_swar16_kernel(SearchParams P, uint32_t delta, uint32_t *nul_flag) {
-    const uint64_t lane_id = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    const uint64_t byte0 = lane_id * 16u;                       // in the address space of hay - delta
-    const uint32_t n = P.needle_len, k = P.k;
-    const uint64_t h = P.hay_len, last = h - n, end = (uint64_t)delta + h;   // bytes [delta, end) are the haystack; 16 bytes of slack follow
-    if (byte0 >= end) return;                                   // (the lanes behind the last offset still check their bytes for NUL)
-    uint32_t nd12[NW], tail_mask, tail_pad;
-    ham_swar_needle<NW>(P.needle, n, nd12, tail_mask, tail_pad);
-    typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(16)));
-    const u32x4a *src = (const u32x4a *)(P.hay - delta + byte0);
-    constexpr int NQ = (4 + NW + 3) / 4;
-    u32x4a q[NQ];
-#pragma unroll
-    for (int t = 0; t < NQ; t++) q[t] = (byte0 + 16u * (uint64_t)t <= end) ? src[t] : u32x4a{0u, 0u, 0u, 0u};
-    uint32_t w[4 + NW];
-#pragma unroll
-    for (int i = 0; i < 4 + NW; i++) w[i] = q[i >> 2][i & 3];
-    if (nul_flag) {                                             // bytes byte0 .. byte0 + 15 are this lane's to check
-        bool z;
-        if (byte0 >= delta && byte0 + 16u <= end) {
-            z = (ham_ne12(w[0] ^ 0x0C0C0C0Cu) & ham_ne12(w[1] ^ 0x0C0C0C0Cu) & ham_ne12(w[2] ^ 0x0C0C0C0Cu) & ham_ne12(w[3] ^ 0x0C0C0C0Cu)) != 0xFFFFFFFFu;
-        } else {
-            z = false;
-            for (uint32_t b = 0; b < 16u; b++) {
-                const uint64_t x = byte0 + b;
-                if (x >= delta && x < end) z |= ((w[b >> 2] >> (8u * (b & 3u))) & 0xFFu) == 0u;
-            }
-        }
-        if (z) atomicOr(nul_flag, 1u);
-    }
-    uint32_t cnt[16];
-    ham_swar_lane<NW>(w, nd12, tail_mask, tail_pad, cnt);
-    // the counts are 8 x the mismatches: one minimum over the sixteen (v_min3) against 8 k + 7 decides whether the lane reports at all
-    const uint32_t thr = k >= 0x1FFFFFFFu ? 0xFFFFFFFFu : 8u * k + 7u;
-    auto min3 = [](uint32_t a, uint32_t b, uint32_t c) { const uint32_t m = a < b ? a : b; return m < c ? m : c; };
-    const uint32_t m0 = min3(cnt[0], cnt[1], cnt[2]), m1 = min3(cnt[3], cnt[4], cnt[5]), m2 = min3(cnt[6], cnt[7], cnt[8]),
-                   m3 = min3(cnt[9], cnt[10], cnt[11]), m4 = min3(cnt[12], cnt[13], cnt[14]);
-    if (min3(min3(m0, m1, m2), min3(m3, m4, cnt[15]), 0xFFFFFFFFu) > thr) return;
-#pragma unroll 1
-    for (uint32_t o = 0; o < 16u; o++) {
-        const uint64_t x = byte0 + o;
-        if (cnt[o] > thr || x < delta || x - delta > last) continue;
-        const uint64_t pos = x - delta;
-        unsigned long long idx = atomicAdd(P.count, 1ull);
-        if (idx < P.cap) P.hits[idx] = ta_match{P.base + pos, P.base + pos + n, cnt[o] >> 3, 0u};
-    }
-}
-
-// needles of 9..32 bytes with a small k, bit-sliced counters (ham_bits_body.h): one lane per tile of P.tile bytes (a multiple of 128), the
-// 256-entry Mis table once per lane in LDS (64 KB, 512 threads: two workgroups per CU), a whole 128-byte line per lane per burst one line
-// ahead.  The NUL-byte scan rides along (the lane checks the bytes of its own tile).
-template <int B>
-__global__ __launch_bounds__(512) void hamming_search_bits_kernel(SearchParams P, uint32_t *nul_flag) {
-    __shared__ __attribute__((aligned(16))) uint32_t mis[256 * 64];
-    {
-        const uint32_t m = ham_bits_mis(P.needle, P.needle_len, threadIdx.x >> 1);
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 *row = (u32x4 *)(mis + (threadIdx.x >> 1) * 64 + (threadIdx.x & 1u) * 32);
-#pragma unroll
-        for (int q = 0; q < 8; q++) row[q] = u32x4{m, m, m, m};
-    }
-    __syncthreads();
-    const uint32_t lane_off = (threadIdx.x & 63u) * 4u;
-    auto lookup = [&](uint32_t v, int b) -> uint32_t {
-        const uint32_t a = __builtin_amdgcn_perm(v, lane_off, 0x0C0C0000u | ((4u + (uint32_t)b) << 8));   // lane*4 | byte b << 8
-        return *(const uint32_t *)((const uint8_t *)mis + a);
-    };
-    const uint32_t n = P.needle_len, k = P.k;
-    const uint64_t h = P.hay_len, last = h - n;
-    const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t b0 = tile * P.tile;                             // this lane reports the alignments that END at bytes [b0, b1)
-    if (b0 >= h) return;
-    const uint64_t b1 = b0 + P.tile < h ? b0 + P.tile : h;
-    const uint8_t *hay = P.hay;
-    HamBitsState<B> st;
-    ham_bits_reset<B>(st, n);
-    uint32_t bias[B];
-    ham_bits_bias<B>(k, n, bias);
-    for (uint64_t i = b0 > n - 1u ? b0 - (n - 1u) : 0; i < b0; i++) ham_bits_step<B>(st, lookup(hay[i], 0), bias);   // the n - 1 bytes in front
-    auto report = [&](uint64_t x) {                                // the alignment ending at byte x has at most k mismatches
-        if (x < n - 1u) return;                                    // (no alignment ends there: the verdict bits of a haystack's first bytes)
-        const uint64_t pos = x - (n - 1u);
-        if (pos > last) return;
-        uint32_t cnt = 0;
-        for (uint32_t j = 0; j < n; j++) cnt += hay[pos + j] != P.needle[j];           // (n <= 32: the kernarg copy)
-        const unsigned long long idx = atomicAdd(P.count, 1ull);
-        if (idx < P.cap) P.hits[idx] = ta_match{P.base + pos, P.base + pos + n, cnt, 0u};
-    };
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-    uint64_t i = b0;
-    const uint64_t full_end = b0 + ((b1 - b0) & ~(uint64_t)127);
-    uint32_t nz = 0xFFFFFFFFu;                                     // AND of the byte tests: 0xFF per byte that is not NUL
-    u32x4u nxt[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) nxt[q] = (i + 16u * q < b1) ? *(const u32x4u *)(hay + i + 16u * q) : u32x4u{0, 0, 0, 0};
-    while (i < full_end) {                                         // whole lines
-        u32x4u cur[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) cur[q] = nxt[q];
-#pragma unroll
-        for (int q = 0; q < 8; q++)                                // blobs carry 16 bytes of slack
-            if (i + 128u + 16u * q < b1) nxt[q] = *(const u32x4u *)(hay + i + 128u + 16u * q);
-#pragma unroll 1
-        for (int part = 0; part < 4; part++) {                     // 32 bytes = 32 verdicts per register
-            uint32_t acc = 0;
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const u32x4u v = part == 0 ? cur[q] : part == 1 ? cur[2 + q] : part == 2 ? cur[4 + q] : cur[6 + q];
-#pragma unroll
-                for (int b = 0; b < 16; b++) {
-                    const uint32_t ov = ham_bits_step<B>(st, lookup(v[b >> 2], b & 3), bias);
-                    acc = __builtin_amdgcn_alignbit(acc, ov, 31);   // (acc << 1) | (ov >> 31)
-                }
-                if (nul_flag) nz &= __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[0] ^ 0x0C0C0C0Cu) & __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[1] ^ 0x0C0C0C0Cu) &
-                                    __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[2] ^ 0x0C0C0C0Cu) & __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[3] ^ 0x0C0C0C0Cu);
-            }
-            if (acc != 0xFFFFFFFFu)                                // bit 31 - t = the verdict of byte i + 32 part + t
-                for (uint32_t t = 0; t < 32u; t++)
-                    if (!((acc >> (31u - t)) & 1u)) report(i + 32u * (uint32_t)part + t);
-        }
-        i += 128;
-    }
-    for (; i < b1; i++) {                                          // the tile's last, partial line
-        const uint32_t c = hay[i];
-        if (!(ham_bits_step<B>(st, lookup(c, 0), bias) >> 31)) report(i);
-        if (nul_flag && c == 0u) nz = 0;
-    }
-    if (nul_flag && nz != 0xFFFFFFFFu) atomicOr(nul_flag, 1u);
-}
-
-// Bit-sliced counters over a subset of the needle's positions, Q phases per dword (ham_phase_body.h): any needle length; one lane per tile of
-// P.tile bytes (a multiple of 128), the 256-entry phase-0 Mis table once per lane in LDS (64 KB, 512 threads), a whole 128-byte line per
-// lane per burst one line ahead.  A 16-byte piece is 16 / Q steps whose verdict words are AND-ed: only a piece that holds a candidate looks
-// at them one by one, and a candidate is recounted over the whole needle.  The NUL-byte scan rides along.
-template <int Q, int B>
-__global__ __launch_bounds__(512) void hamming_search_phase_kernel(SearchParams P, HamPhaseGeom G, uint32_t *nul_flag) {
-    __shared__ __attribute__((aligned(16))) uint32_t mis[256 * 64];
-    {
-        const uint32_t m = ham_phase_mis(P.needle_len <= 64u ? P.needle : P.needle_dev, G, threadIdx.x >> 1);   // (up to 64 bytes: the kernarg copy, no upload)
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 *row = (u32x4 *)(mis + (threadIdx.x >> 1) * 64 + (threadIdx.x & 1u) * 32);
-#pragma unroll
-        for (int q = 0; q < 8; q++) row[q] = u32x4{m, m, m, m};
-    }
-    __syncthreads();
-    constexpr uint32_t W = 32u / Q, STEPS = 16u / Q;
-    const uint32_t lane_off = (threadIdx.x & 63u) * 4u;
-    auto lookup = [&](uint32_t v, int b) -> uint32_t {
-        const uint32_t a = __builtin_amdgcn_perm(v, lane_off, 0x0C0C0000u | ((4u + (uint32_t)b) << 8));   // lane*4 | byte b << 8
-        return *(const uint32_t *)((const uint8_t *)mis + a);
-    };
-    const uint32_t n = P.needle_len, k = P.k, keep = G.keep, span = G.span;
-    const uint64_t h = P.hay_len, last = h - n;
-    const uint64_t tile = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t b0 = tile * P.tile;                             // this lane reports the alignments whose VERDICT byte is in [b0, b1)
-    if (b0 >= h) return;
-    const uint64_t b1 = b0 + P.tile < h ? b0 + P.tile : h;
-    const uint8_t *hay = P.hay;
-    HamBitsState<B> st;
-    ham_phase_reset<B>(st, G);
-    uint32_t bias[B];
-    ham_phase_bias<B>(k, G, bias);
-    auto bytes_step = [&](uint64_t i) -> uint32_t {                // one step from single bytes (warm-up, the last partial line)
-        uint32_t m = 0;
-#pragma unroll
-        for (int r = Q - 1; r >= 0; r--) {
-            const uint32_t c = i + (uint32_t)r < h ? hay[i + (uint32_t)r] : 0u;
-            const uint32_t t = lookup(c, 0);
-            m = Q == 1 ? t : ((m << (W & 31u)) | t);
-        }
-        return ham_phase_step<B, (Q > 1)>(st, m, bias, keep);
-    };
-    for (uint64_t i = b0 > span ? b0 - span : 0; i < b0; i += Q) bytes_step(i);   // the span bytes in front (b0 and span are multiples of Q)
-    auto verify = [&](uint64_t x) {                                // the alignment whose verdict byte is x passed the filter
-        if (x < span) return;                                      // (no alignment ends there: the verdict bits of a haystack's first bytes)
-        const uint64_t pos = x - span;
-        if (pos > last) return;
-        uint32_t cnt = 0;
-        const uint8_t *nd = n <= 64u ? P.needle : P.needle_dev;
-        for (uint32_t j = 0; j < n; j++) cnt += hay[pos + j] != nd[j];
-        if (cnt > k) return;
-        const unsigned long long idx = atomicAdd(P.count, 1ull);
-        if (idx < P.cap) P.hits[idx] = ta_match{P.base + pos, P.base + pos + n, cnt, 0u};
-    };
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-    uint64_t i = b0;
-    const uint64_t full_end = b0 + ((b1 - b0) & ~(uint64_t)127);
-    uint32_t nz = 0xFFFFFFFFu;                                     // AND of the byte tests: 0xFF per byte that is not NUL
-    u32x4u nxt[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) nxt[q] = (i + 16u * q < b1) ? *(const u32x4u *)(hay + i + 16u * q) : u32x4u{0, 0, 0, 0};
-    while (i < full_end) {                                         // whole lines
-        u32x4u cur[8];
-#pragma unroll
-        for (int q = 0; q < 8; q++) cur[q] = nxt[q];
-#pragma unroll
-        for (int q = 0; q < 8; q++)                                // blobs carry 16 bytes of slack
-            if (i + 128u + 16u * q < b1) nxt[q] = *(const u32x4u *)(hay + i + 128u + 16u * q);
-#pragma unroll 1
-        for (int part = 0; part < 4; part++) {
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const u32x4u v = part == 0 ? cur[q] : part == 1 ? cur[2 + q] : part == 2 ? cur[4 + q] : cur[6 + q];
-                // windows of at most 8 steps: their verdict words are kept (8 registers) and AND-ed; only a window that holds a candidate
-                // looks at them one by one
-                constexpr uint32_t WIN = STEPS > 8u ? 8u : STEPS;
-#pragma unroll
-                for (uint32_t w0 = 0; w0 < STEPS; w0 += WIN) {
-                    uint32_t ov[WIN];
-#pragma unroll
-                    for (uint32_t s = 0; s < WIN; s++) {
-                        uint32_t m = 0;
-#pragma unroll
-                        for (int r = Q - 1; r >= 0; r--) {
-                            const uint32_t b = Q * (w0 + s) + (uint32_t)r;
-                            const uint32_t t = lookup(v[b >> 2], b & 3);
-                            m = Q == 1 ? t : ((m << (W & 31u)) | t);
-                        }
-                        ov[s] = ham_phase_step<B, (Q > 1)>(st, m, bias, keep);
-                    }
-                    uint32_t all = ov[0];
-#pragma unroll
-                    for (uint32_t s = 1; s < WIN; s++) all &= ov[s];
-                    if ((all | keep) != 0xFFFFFFFFu) {              // a phase top that is clear: a candidate somewhere in this window
-                        uint32_t cm = 0;                           // bit Q s + r: the verdict of byte Q (w0 + s) + r of the piece
-#pragma unroll
-                        for (uint32_t s = 0; s < WIN; s++) {
-                            uint32_t o = ov[s];
-                            asm volatile("" : "+v"(o));             // (keeps the sorting of the verdicts inside the rare branch: hipcc hoists it otherwise)
-#pragma unroll
-                            for (uint32_t r = 0; r < (uint32_t)Q; r++)
-                                cm |= ((~o >> (r * W + W - 1u)) & 1u) << (Q * s + r);
-                        }
-                        const uint64_t first = i + 32u * (uint32_t)part + 16u * (uint32_t)q + Q * w0;
-                        while (cm) {
-                            const uint32_t t = (uint32_t)__builtin_ctz(cm);
-                            cm &= cm - 1u;
-                            verify(first + t);
-                        }
-                    }
-                }
-                if (nul_flag) nz &= __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[0] ^ 0x0C0C0C0Cu) & __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[1] ^ 0x0C0C0C0Cu) &
-                                    __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[2] ^ 0x0C0C0C0Cu) & __builtin_amdgcn_perm(0xFFFFFFFFu, 0xFFFFFFFFu, v[3] ^ 0x0C0C0C0Cu);
-            }
-        }
-        i += 128;
-    }
-    for (; i < b1; i += Q) {                                       // the tile's last, partial line, step by step
-        const uint32_t ov = bytes_step(i);
-#pragma unroll
-        for (uint32_t r = 0; r < (uint32_t)Q; r++) {
-            if (!((ov >> (r * W + W - 1u)) & 1u)) verify(i + r);
-            if (nul_flag && i + r < h && hay[i + r] == 0u) nz = 0;
-        }
-    }
-    if (nul_flag && nz != 0xFFFFFFFFu) atomicOr(nul_flag, 1u);
-}
-
-// needles of up to 32 bytes: shift-add scan (ham_search_body.h), one lane per tile of P.tile offsets, table in LDS,
-// haystack requested 64 bytes per lane one block ahead
-template <int NWS>
-__global__ __launch_bounds__(256) void hamming_search_sa_kernel(SearchParams P) {
-    __shared__ uint32_t tab[256 * NWS];
-    for (int w = 0; w < NWS; w++) tab[threadIdx.x * NWS + w] = ham_sa_table_word(P.needle, P.needle_len, threadIdx.x, w);
-    __syncthreads();
-    const uint32_t n = P.needle_len, k = P.k;
-    const uint64_t offsets = P.hay_len - n + 1;
-    const uint64_t ob = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * P.tile;
-    if (ob >= offsets) return;
-    const uint64_t oe = ob + P.tile < offsets ? ob + P.tile : offsets;
-    const uint8_t *hay = P.hay;
-    HamSaState<NWS> st;
-#pragma unroll
-    for (int w = 0; w < NWS; w++) st.S[w] = 0;
-    auto stepc = [&](uint32_t c) -> uint32_t {
-        uint32_t Tc[NWS];
-#pragma unroll
-        for (int w = 0; w < NWS; w++) Tc[w] = tab[c * NWS + w];
-        return ham_sa_step<NWS>(st, Tc, n);
-    };
-    auto emit = [&](uint64_t p, uint32_t cnt) {
-        unsigned long long idx = atomicAdd(P.count, 1ull);
-        if (idx < P.cap) P.hits[idx] = ta_match{P.base + p, P.base + p + n, cnt, 0u};
-    };
-    uint64_t i = ob;
-    for (; i < ob + (n - 1); i++) stepc(hay[i]);                  // the first n-1 bytes complete no offset
-    const uint64_t end = oe + (n - 1);                            // one past the last byte this tile reads
-    typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-    const uint64_t full_end = i + ((end - i) & ~(uint64_t)63);
-    u32x4u nxt[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) nxt[q] = (i + 16u * q < end) ? *(const u32x4u *)(hay + i + 16u * q) : u32x4u{0, 0, 0, 0};
-    while (i < full_end) {
-        u32x4u cur[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) cur[q] = nxt[q];
-#pragma unroll
-        for (int q = 0; q < 4; q++)                               // blobs carry 16 bytes of slack
-            if (i + 64u + 16u * q < end) nxt[q] = *(const u32x4u *)(hay + i + 64u + 16u * q);
-#pragma unroll 1
-        for (int q = 0; q < 4; q++) {
-#pragma unroll
-            for (int b = 0; b < 16; b++) {
-                const uint32_t cnt = stepc((cur[q][b >> 2] >> (8 * (b & 3))) & 0xffu);
-                if (cnt <= k) emit(i + 16u * q + b - (n - 1), cnt);
-            }
-        }
-        i += 64;
-    }
-    for (; i < end; i++) {
-        const uint32_t cnt = stepc(hay[i]);
-        if (cnt <= k) emit(i - (n - 1), cnt);
-    }
-}
-
-// nul_flag: where the kernel reports a zero byte in the haystack (nullptr: no check wanted); *nul_done = the launch did the check
-hipError_t hamming_search_launch(const SearchParams &P0, hipStream_t s, uint32_t *nul_flag, bool *nul_done) {
-    SearchParams P = P0;
-    if (nul_done) *nul_done = false;
-    if (P.hay_len < P.needle_len || P.needle_len == 0) return hipSuccess;
-    // needles of 9..32 bytes whose k needs few counter bits: bit-sliced counters, 3 B + 3 instructions per byte against the SWAR form's
-    // 3 per needle dword + 3 (TA_HAMMING_SEARCH_NO_BITS=1 keeps the SWAR form)
-    // bit-sliced counters over a subset of the needle's positions, Q phases per dword (ham_phase_body.h): any needle length, where the
-    // subset is selective for k and the form costs fewer instructions per byte than the SWAR form (TA_HAMMING_SEARCH_NO_PHASE=1: without)
-    {
-        uint32_t Q = 0, L = 0; int B = 0;
-        const uint32_t swar_x4 = 4u * (3u * ((P.needle_len + 3u) / 4u) + 4u);
-        if ((P.needle_dev || P.needle_len <= 64u) && ham_phase_plan(P.needle_len, P.k, Q, L, B) && (P.needle_len > 64u || ham_phase_cost_x4(Q, B) < swar_x4) &&
-            !env_str("TA_HAMMING_SEARCH_SWAR") && !env_str("TA_HAMMING_SEARCH_SA") && !env_str("TA_HAMMING_SEARCH_NO_BITS") &&
-            !env_str("TA_HAMMING_SEARCH_NO_PHASE")) {
-            if (const char *fq = env_str("TA_HAMMING_PHASE_Q")) {                    // tests: force fewer phases (1 or 2) where the plan allows them
-                const uint32_t q = (uint32_t)atoi(fq);
-                if ((q == 1u || q == 2u) && q < Q) {
-                    uint32_t l = (P.needle_len + q - 1u) / q;
-                    if (l > 32u / q) l = 32u / q;
-                    Q = q; L = l;
-                }
-            }
-            const HamPhaseGeom G = ham_phase_geom(Q, L);
-            uint64_t tile = (P.hay_len + 262143) / 262144;            // two sets of resident lanes
-            tile = (tile + 127) & ~(uint64_t)127;
-            if (tile < 256) tile = 256;
-            P.tile = (uint32_t)(tile > 0x7FFFFF80ull ? 0x7FFFFF80ull : tile);
-            const uint64_t lanes = (P.hay_len + P.tile - 1) / P.tile;
-            const dim3 grid((uint32_t)((lanes + 511) / 512)), block(512);
-            if (nul_done) *nul_done = nul_flag != nullptr;
-            set_last_kernel_name("hamming_search_phase_kernel<%u,%d>", Q, B);
-#define TA_HP(QQ, BB) hipLaunchKernelGGL((hamming_search_phase_kernel<QQ, BB>), grid, block, 0, s, P, G, nul_flag)
-#define TA_HPB(QQ) switch (B) { case 1: TA_HP(QQ, 1); break; case 2: TA_HP(QQ, 2); break; case 3: TA_HP(QQ, 3); break; case 4: TA_HP(QQ, 4); break; default: TA_HP(QQ, 5); break; }
-            if (Q == 4u) { TA_HPB(4) } else if (Q == 2u) { TA_HPB(2) } else { TA_HPB(1) }
-#undef TA_HPB
-#undef TA_HP
-            return hipGetLastError();
-        }
-    }
-    const int planes = ham_bits_planes(P.k);
-    if (P.needle_len >= 9 && P.needle_len <= 32 && planes && P.k < P.needle_len && 3 * planes + 3 < 3 * (int)((P.needle_len + 3) / 4) + 1 &&
-        !env_str("TA_HAMMING_SEARCH_SWAR") && !env_str("TA_HAMMING_SEARCH_SA") && !env_str("TA_HAMMING_SEARCH_NO_BITS")) {
-        uint64_t tile = (P.hay_len + 262143) / 262144;            // two sets of resident lanes
-        tile = (tile + 127) & ~(uint64_t)127;
-        if (tile < 256) tile = 256;
-        P.tile = (uint32_t)(tile > 0x7FFFFF80ull ? 0x7FFFFF80ull : tile);
-        const uint64_t lanes = (P.hay_len + P.tile - 1) / P.tile;
-        const dim3 grid((uint32_t)((lanes + 511) / 512)), block(512);
-        if (nul_done) *nul_done = nul_flag != nullptr;
-        set_last_kernel_name("hamming_search_bits_kernel<%d>", planes);
-        switch (planes) {
-            case 1: hipLaunchKernelGGL(hamming_search_bits_kernel<1>, grid, block, 0, s, P, nul_flag); break;
-            case 2: hipLaunchKernelGGL(hamming_search_bits_kernel<2>, grid, block, 0, s, P, nul_flag); break;
-            case 3: hipLaunchKernelGGL(hamming_search_bits_kernel<3>, grid, block, 0, s, P, nul_flag); break;
-            case 4: hipLaunchKernelGGL(hamming_search_bits_kernel<4>, grid, block, 0, s, P, nul_flag); break;
-            default: hipLaunchKernelGGL(hamming_search_bits_kernel<5>, grid, block, 0, s, P, nul_flag); break;
-        }
-        return hipGetLastError();
-    }
-    if (P.needle_len <= 64 && !env_str("TA_HAMMING_SEARCH_SWAR") && !env_str("TA_HAMMING_SEARCH_SA")) {
-        const uint32_t delta = (uint32_t)((uintptr_t)P.hay & 15u);
-        const uint64_t lanes = (P.hay_len + delta + 15) / 16;
-        const dim3 grid((uint32_t)((lanes + 255) / 256)), block(256);
-        if (nul_done) *nul_done = nul_flag != nullptr;
-        set_last_kernel_name("hamming_search_swar16_kernel<%u>", (P.needle_len + 3) / 4);
-        switch ((P.needle_len + 3) / 4) {
-#define TA_HS(NW) case NW: hipLaunchKernelGGL(hamming_search_swar16_kernel<NW>, grid, block, 0, s, P, delta, nul_flag); break;
-            TA_HS(1) TA_HS(2) TA_HS(3) TA_HS(4) TA_HS(5) TA_HS(6) TA_HS(7) TA_HS(8)
-            TA_HS(9) TA_HS(10) TA_HS(11) TA_HS(12) TA_HS(13) TA_HS(14) TA_HS(15) TA_HS(16)
-#undef TA_HS
-        }
-        return hipGetLastError();
-    }
-    if (P.needle_len <= 32 && !env_str("TA_HAMMING_SEARCH_SWAR")) {
-        const uint64_t offsets = P.hay_len - P.needle_len + 1;
-        uint64_t tile = (offsets + 262143) / 262144;              // two sets of resident lanes
-        if (tile < 8ull * P.needle_len) tile = 8ull * P.needle_len;
-        if (tile < 64) tile = 64;
-        P.tile = (uint32_t)(tile > 0x7FFFFFFFull ? 0x7FFFFFFFull : tile);
-        const uint64_t lanes = (offsets + P.tile - 1) / P.tile;
-        const uint32_t grid = (uint32_t)((lanes + 255) / 256);
-        const uint32_t nws = (P.needle_len + 3) / 4;
-        set_last_kernel_name("hamming_search_sa_kernel<%u>", nws <= 2 ? 2u : nws <= 4 ? 4u : 8u);
-        if (nws <= 2) hipLaunchKernelGGL(hamming_search_sa_kernel<2>, dim3(grid), dim3(256), 0, s, P);
-        else if (nws <= 4) hipLaunchKernelGGL(hamming_search_sa_kernel<4>, dim3(grid), dim3(256), 0, s, P);
-        else hipLaunchKernelGGL(hamming_search_sa_kernel<8>, dim3(grid), dim3(256), 0, s, P);
-        return hipGetLastError();
-    }
-    const uint32_t delta = (uint32_t)((uintptr_t)P.hay & 3u);
-    const uint64_t groups = (P.hay_len - P.needle_len + delta) / 4 + 1;
-    set_last_kernel_name("hamming_search_kernel");
-    hipLaunchKernelGGL(hamming_search_kernel, dim3((uint32_t)((groups + 255) / 256)), dim3(256), 0, s, P, delta);
-    return hipGetLastError();
-}
-
-// A search's outcome into host-mapped pinned memory (one 256-thread block behind the search kernel on its stream): the hit count, the
-// NUL-byte flag and -- when they are few enough for the box -- the hit records themselves: the host has everything after ONE stream
-// synchronisation, no copy (a count brought back by hipMemcpyAsync into pageable memory + a device-side sort and copy of the hits cost
-// a hamming_search call 0.11 ms beyond its kernel).
-__global__ void search_report_copy_kernel(const unsigned long long *count, const uint32_t *nul_flag, const ta_match *hits, uint64_t cap, uint8_t *box) {
-    SearchReport *rep = (SearchReport *)box;
-    const unsigned long long c = *count;
-    const uint64_t have = c < cap ? c : cap;
-    const bool fits = have <= SEARCH_REPORT_SEL;
-    if (threadIdx.x == 0) {
-        rep->count = c;
-        rep->dense = nul_flag ? *nul_flag : 0u;        // (this report: a NUL byte in the haystack)
-        rep->sel_count = fits ? (uint32_t)have : 0u;
-        rep->sel_state = fits ? 1u : 2u;               // 1: the records follow this header; 2: too many, they are in the caller's device buffer
-    }
-    if (!fits) return;
-    uint64_t *dst = (uint64_t *)(box + sizeof(SearchReport));
-    const uint64_t *src = (const uint64_t *)hits;
-    for (uint64_t w = threadIdx.x; w < have * 3u; w += blockDim.x) dst[w] = src[w];
-}
-hipError_t search_report_copy_launch(const unsigned long long *count, const uint32_t *nul_flag, const ta_match *hits, uint64_t cap, uint8_t *box, hipStream_t s) {
-    hipLaunchKernelGGL(search_report_copy_kernel, dim3(1), dim3(256), 0, s, count, nul_flag, hits, cap, box);
-    return hipGetLastError();
-}
-
-// check_no_null_bytes (src/lib.rs:237-243) over device memory: *flag != 0 iff a zero byte exists
-__global__ void has_zero_byte_kernel(const uint8_t *p, uint64_t len, uint32_t *flag) {
-    uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    bool z = false;
-    if (i + 16 <= len) {
-        typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
-        u32x4u v = *(const u32x4u *)(p + i);
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            uint32_t x = v[w];
-            z |= ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u) != 0x80808080u;
-        }
-    } else {
-        for (uint64_t t = i; t < len; t++) z |= (p[t] == 0);
-    }
-    if (z) atomicOr(flag, 1u);
-}
-hipError_t has_zero_byte_launch(const uint8_t *p, uint64_t len, uint32_t *flag, hipStream_t s) {
-    if (len == 0) return hipSuccess;
-    uint64_t threads = (len + 15) / 16;
-    hipLaunchKernelGGL(has_zero_byte_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, p, len, flag);
     return hipGetLastError();
 }
 

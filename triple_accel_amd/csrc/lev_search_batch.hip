@@ -7,6 +7,7 @@
 #include <stddef.h>
 
 #include "dev_str.h"
+#include "lds_tab64.h"
 #include "lev_search_batch_body.h"
 #include "ta_internal.h"
 
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(256) void lev_search_batch_mem_kernel(SearchBatchPa
 }
 
 // Route S scan: one lane per pair over its haystack.  The shared needle's match table is built once per workgroup in LDS; NWF = 1
-// keeps it 64 times (lev_filter_kernel's REPL layout: lane l reads dword l of row c, no two lanes of a 32-lane group share a bank
+// keeps it once per lane of a wavefront (lds_tab64.h: lane l reads dword l of row c, no two lanes of a 32-lane group share a bank
 // whatever the bytes are), NWF = 2 keeps one [256][2] table.  Pairs with a candidate end get their span and a place in the list;
 // the others are finished here: their result is the end == 0 match or nothing.
 template <int NWF, bool TRANS>
@@ -85,12 +86,8 @@ __global__ __launch_bounds__(NWF == 1 ? 512 : 256) void lev_search_batch_scan_ke
     __shared__ __attribute__((aligned(16))) uint32_t peq[NWF == 1 ? 256 * 64 : 256 * 2];
     const uint8_t *needle = P.nd.blob;
     const uint32_t nlen = (uint32_t)P.nd.len;
-    if (NWF == 1) {                          // 512 threads: two per row, half a row each
-        const uint32_t m = lev_filter_peq(needle, nlen, threadIdx.x >> 1);
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-        u32x4 *row = (u32x4 *)(peq + (threadIdx.x >> 1) * 64 + (threadIdx.x & 1u) * 32);
-#pragma unroll
-        for (int q = 0; q < 8; q++) row[q] = u32x4{m, m, m, m};
+    if (NWF == 1) {
+        tab64_fill(peq, lev_filter_peq(needle, nlen, threadIdx.x >> 1));
     } else {
         peq[2 * threadIdx.x] = lev_filter_peq_word(needle, nlen, 2, threadIdx.x, 0);
         peq[2 * threadIdx.x + 1] = lev_filter_peq_word(needle, nlen, 2, threadIdx.x, 1);

@@ -338,8 +338,12 @@ void search_resident_reset();        // forget what ta_levenshtein_search_first 
 hipError_t lev_search_wave_launch(const SearchParams &P, bool trans, bool best, const uint32_t *list, uint32_t cap_list,
                                   SearchCtl *ctl, SearchSlot *slots /* SEARCH_SLOT_CAP of them; Best passes */, uint8_t *report_dev,
                                   hipStream_t s);
+// util_kernels.hip: a search's count, NUL flag and (few) hits into the report box; *flag != 0 iff p[0 .. len) holds a zero byte
 hipError_t search_report_copy_launch(const unsigned long long *count, const uint32_t *nul_flag, const ta_match *hits, uint64_t cap, uint8_t *box, hipStream_t s);
-hipError_t hamming_search_launch(const SearchParams &P, hipStream_t s, uint32_t *nul_flag = nullptr, bool *nul_done = nullptr);
+hipError_t has_zero_byte_launch(const uint8_t *p, uint64_t len, uint32_t *flag, hipStream_t s);
+// ham_search.hip: the kernel `route` names (ham_search_plan.h; P.needle_dev set where it needs it).  nul_flag: nullptr = no check wanted
+struct HamSearchRoute;
+hipError_t hamming_search_launch(const SearchParams &P, const HamSearchRoute &route, hipStream_t s, uint32_t *nul_flag = nullptr);
 
 // ta_levenshtein_search_batch (lev_search_batch.hip): one lane per (needle, haystack) pair
 struct SearchBatchParams {

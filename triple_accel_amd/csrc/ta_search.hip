@@ -8,12 +8,12 @@
 #include <algorithm>
 #include <vector>
 
+#include "ham_search_plan.h"
 #include "lev_filter_body.h"
 #include "lev_search_body.h"
 #include "ta_internal.h"
 
 namespace ta {
-hipError_t has_zero_byte_launch(const uint8_t *p, uint64_t len, uint32_t *flag, hipStream_t s);
 
 // tile size: enough tiles to fill the chip (>= ~128K lanes) while keeping the halo overhead small
 static uint32_t pick_tile(uint64_t hay_len, uint32_t halo) {
@@ -287,10 +287,15 @@ static int hamming_search_dev_impl(const uint8_t *needle_host, size_t needle_len
     SearchParams P;
     fill_params(P, needle_host, needle_len, haystack_dev, haystack_len, k, nullptr, 0, base, 0, hits_dev, cap,
                 (unsigned long long *)cnt.dev);
+    HamSearchSwitches sw{};
+    sw.swar = env_str("TA_HAMMING_SEARCH_SWAR") != nullptr; sw.sa = env_str("TA_HAMMING_SEARCH_SA") != nullptr;
+    sw.no_bits = env_str("TA_HAMMING_SEARCH_NO_BITS") != nullptr; sw.no_phase = env_str("TA_HAMMING_SEARCH_NO_PHASE") != nullptr;
+    if (const char *q = env_str("TA_HAMMING_PHASE_Q")) sw.phase_q = (uint32_t)atoi(q);
+    const HamSearchRoute route = ham_search_route((uint32_t)needle_len, k, sw);
     // needles of up to 64 bytes travel in the kernel arguments (SearchParams::needle): no upload
-    // (the round-1 SWAR kernel -- needles beyond 64 bytes the phased filter does not take, or TA_HAMMING_SEARCH_SWAR=1 -- reads the device copy)
+    // (the round-1 SWAR kernel, and the phased filter beyond 64 bytes, read the device copy)
     P.needle_dev = nullptr;
-    if (needle_len > 64 || env_str("TA_HAMMING_SEARCH_SWAR") || (needle_len > 32 && tuning_enabled())) {   // (any A/B switch may route to the kernel that reads the device copy)
+    if (route.needs_needle_dev) {
         Scratch &nd = tls_scratch(SLOT_AUX_A);
         if ((rc = nd.ensure(needle_len + 16))) return rc;
         TA_HIP(hipMemcpyAsync(nd.dev, needle_host, needle_len, hipMemcpyHostToDevice, st));
@@ -298,9 +303,8 @@ static int hamming_search_dev_impl(const uint8_t *needle_host, size_t needle_len
     }
     // the NUL-byte scan of the SIMD contract (:463) rides inside the search kernel where that kernel reads every byte anyway
     uint32_t *nul_flag = (uint32_t *)((uint8_t *)cnt.dev + 8);
-    bool nul_done = false;
-    TA_HIP(hamming_search_launch(P, st, check_nul ? nul_flag : nullptr, &nul_done));
-    if (check_nul && !nul_done) TA_HIP(has_zero_byte_launch(haystack_dev, haystack_len, nul_flag, st));
+    TA_HIP(hamming_search_launch(P, route, st, check_nul ? nul_flag : nullptr));
+    if (check_nul && !route.scans_nul) TA_HIP(has_zero_byte_launch(haystack_dev, haystack_len, nul_flag, st));
     // count, NUL flag and (few) hits into host-mapped memory: one synchronisation delivers them
     TA_HIP(search_report_copy_launch((const unsigned long long *)cnt.dev, nul_flag, hits_dev, cap, box.dev, st));
     TA_HIP(hipStreamSynchronize(st));

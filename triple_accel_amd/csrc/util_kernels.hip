@@ -1,4 +1,4 @@
-// util_kernels.hip -- Hamming batch kernel (HBM-bound) and the small helper kernels of the batch API.
+// util_kernels.hip -- Hamming batch kernel (HBM-bound) and the small helper kernels of the batch and search API.
 #include <hip/hip_runtime.h>
 
 #include "dev_str.h"
@@ -356,6 +356,55 @@ hipError_t hits_best_launch(const ta_match *hits, uint64_t n, uint32_t *min_k /*
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
     hipLaunchKernelGGL(hits_min_k_kernel, dim3(blocks), dim3(256), 0, st, hits, n, min_k);
     hipLaunchKernelGGL(hits_select_k_kernel, dim3(blocks), dim3(256), 0, st, hits, n, min_k, out, cap, count);
+    return hipGetLastError();
+}
+
+// A search's outcome into host-mapped pinned memory (one 256-thread block behind the search kernel on its stream): the hit count, the
+// NUL-byte flag and -- when they are few enough for the box -- the hit records themselves: the host has everything after ONE stream
+// synchronisation, no copy (a count brought back by hipMemcpyAsync into pageable memory + a device-side sort and copy of the hits cost
+// a hamming_search call 0.11 ms beyond its kernel).
+__global__ void search_report_copy_kernel(const unsigned long long *count, const uint32_t *nul_flag, const ta_match *hits, uint64_t cap, uint8_t *box) {
+    SearchReport *rep = (SearchReport *)box;
+    const unsigned long long c = *count;
+    const uint64_t have = c < cap ? c : cap;
+    const bool fits = have <= SEARCH_REPORT_SEL;
+    if (threadIdx.x == 0) {
+        rep->count = c;
+        rep->dense = nul_flag ? *nul_flag : 0u;        // (this report: a NUL byte in the haystack)
+        rep->sel_count = fits ? (uint32_t)have : 0u;
+        rep->sel_state = fits ? 1u : 2u;               // 1: the records follow this header; 2: too many, they are in the caller's device buffer
+    }
+    if (!fits) return;
+    uint64_t *dst = (uint64_t *)(box + sizeof(SearchReport));
+    const uint64_t *src = (const uint64_t *)hits;
+    for (uint64_t w = threadIdx.x; w < have * 3u; w += blockDim.x) dst[w] = src[w];
+}
+hipError_t search_report_copy_launch(const unsigned long long *count, const uint32_t *nul_flag, const ta_match *hits, uint64_t cap, uint8_t *box, hipStream_t s) {
+    hipLaunchKernelGGL(search_report_copy_kernel, dim3(1), dim3(256), 0, s, count, nul_flag, hits, cap, box);
+    return hipGetLastError();
+}
+
+// check_no_null_bytes (src/lib.rs:237-243) over device memory: *flag != 0 iff a zero byte exists
+__global__ void has_zero_byte_kernel(const uint8_t *p, uint64_t len, uint32_t *flag) {
+    uint64_t i = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    bool z = false;
+    if (i + 16 <= len) {
+        typedef uint32_t u32x4u __attribute__((ext_vector_type(4), aligned(1)));
+        u32x4u v = *(const u32x4u *)(p + i);
+#pragma unroll
+        for (int w = 0; w < 4; w++) {
+            uint32_t x = v[w];
+            z |= ((((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u) != 0x80808080u;
+        }
+    } else {
+        for (uint64_t t = i; t < len; t++) z |= (p[t] == 0);
+    }
+    if (z) atomicOr(flag, 1u);
+}
+hipError_t has_zero_byte_launch(const uint8_t *p, uint64_t len, uint32_t *flag, hipStream_t s) {
+    if (len == 0) return hipSuccess;
+    uint64_t threads = (len + 15) / 16;
+    hipLaunchKernelGGL(has_zero_byte_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, p, len, flag);
     return hipGetLastError();
 }
 
