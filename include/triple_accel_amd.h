@@ -591,6 +591,28 @@ int ta_levenshtein_trace_batch_tokens(const ta_tokens *a, const ta_tokens *b, si
 int ta_levenshtein_tokens(const uint32_t *a, size_t a_len, const uint32_t *b, size_t b_len, uint32_t k,
                           const ta_edit_costs *costs, uint32_t *out, ta_edit **edits, size_t *n_edits);
 
+/* ta_levenshtein_cross_with_opts over token sequences: EVERY query against EVERY target within k, nothing of size nq x nt anywhere
+ * (DESIGN.md 3.20).  The pair (q, t) is a hit with distance d exactly when levenshtein_naive_k_with_opts<u32>(query q, target t, k, false,
+ * costs) is Some(d) (src/levenshtein.rs:376) -- ta_levenshtein_k_batch_tokens' answer for that pair.  *count_dev, hits_dev, cap (0: the
+ * count only), nearest_dev, per_query_dev and flags = TA_CROSS_UPPER are ta_levenshtein_cross_with_opts' word for word, and so are the
+ * costs: LEVENSHTEIN_COSTS, RDAMERAU_COSTS and their multiples (g, g, 0, None | g), run with k / g and reported as g d; other valid costs
+ * are TA_ERR_UNSUPPORTED.
+ * Limits: every query at most 64 tokens -- a longer bound, the strided `len` or a CSR max_len given or measured, is TA_ERR_UNSUPPORTED;
+ * targets of any length below 2^32 items; nq, nt < 2^32.  Both sides take the strided and the CSR form (element offsets, which may start
+ * above 0); no read slack: nothing outside a sequence's items is read.  The CSR field `len` is not needed and is ignored; max_len = 0
+ * costs one synchronisation (both sides are measured together).
+ * Error order, all before any device work: NULL pointers, flags, the costs, the counts / NULL data with nq, nt > 0 / cap with NULL
+ * hits_dev / cap overflow, the length bounds, then TA_ERR_HIP without a device.  nq == 0 or nt == 0: TA_OK, count zero, nearest words all
+ * ones, per-query counts zero.  Asynchronous on `stream`, the counters initialised by kernels: capturable when every length bound is
+ * known.  Inside, a lane owns a target and a wavefront walks a tile of queries as in ta_levenshtein_cross; a query's match vectors come
+ * from a hash table of 256 slots in the wavefront's LDS, keyed by the raw 32-bit values (the per-pair byte codes of the batch entries
+ * cannot be shared among 64 targets).  ta_last_kernel_name: lev_cross_tok_kernel<NW, TRANS>, NW = 1 up to 32 tokens, else 2. */
+int ta_levenshtein_cross_tokens(const ta_tokens *queries, size_t nq, const ta_tokens *targets, size_t nt,
+                                uint32_t k, const ta_edit_costs *costs, uint32_t flags,
+                                ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                uint64_t *nearest_dev    /* nq entries, or NULL */,
+                                uint32_t *per_query_dev  /* nq entries, or NULL */, void *stream);
+
 /* N x hamming(a_i, b_i); out[i] = TA_NONE where the lengths differ (Rust: panic).  Strings below 64 KiB run one wavefront (or a part of
  * one) per pair; longer ones are cut into slices of 16 KiB, one wavefront per slice, the slices of the whole batch spread over the chip
  * (strided: len >= 64 KiB; CSR: the same on the sides' max_len, or up to 8,192 pairs without one; never CSR batches of more than 65,536

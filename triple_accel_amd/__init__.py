@@ -440,6 +440,48 @@ def levenshtein_nearest_with_opts_many(queries, targets, k, costs=LEVENSHTEIN_CO
     return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32, int(c)) for w, c in zip(words, counts)]
 
 
+def _cross_token_sides(queries, targets):
+    """two lists of int sequences (values in [0, 2^32)) or of int32 / int64 tensors -> CSR token sides; an int32 tensor carries its u32
+    bit pattern, as batch.Tokens takes it"""
+    import torch
+    from . import batch as B
+
+    def items(s):
+        if not isinstance(s, torch.Tensor):
+            return s
+        v = s.reshape(-1).tolist()
+        return [x & 0xFFFFFFFF for x in v] if s.dtype == torch.int32 else v
+    return B.Tokens.from_list([items(q) for q in queries]), B.Tokens.from_list([items(t) for t in targets])
+
+
+def levenshtein_cross_tokens_many(queries, targets, k, costs=LEVENSHTEIN_COSTS, upper=False):
+    """levenshtein_cross_with_opts_many over sequences of 32-bit tokens (ta_levenshtein_cross_tokens): the sorted list of (q, t, d) with
+    d = the token edit distance of queries[q] and targets[t] for every pair where it is at most k; upper = True keeps only the pairs
+    with t > q.  The sides are lists of int sequences (values in [0, 2^32)) or of int32 / int64 tensors; queries of at most 64 tokens
+    (swap the sides otherwise).  Both lists are uploaded; when there are more hits than the first call's room, one more call runs with
+    room for the count it reported."""
+    from . import batch as B
+    qs, ts = _cross_token_sides(queries, targets)
+    k = _k(k)
+    hits, count, _, _ = B.levenshtein_cross_tokens(qs, ts, k, costs, upper=upper)
+    n = int(count.cpu()[0].item())
+    if n > hits.shape[0]:
+        hits, count, _, _ = B.levenshtein_cross_tokens(qs, ts, k, costs, cap=n, upper=upper)
+    q, t, d = B.cross_to_arrays(hits, count)
+    return [(int(a), int(b), int(c)) for a, b, c in zip(q, t, d)]
+
+
+def levenshtein_nearest_tokens_many(queries, targets, k, costs=LEVENSHTEIN_COSTS):
+    """For every token query its nearest target within k and how many targets are within k, in ONE device call
+    (ta_levenshtein_cross_tokens, counting only): a list of (target, distance, n_hits) -- the smallest distance, at equal distance the
+    lowest target index -- or None where no target is within k."""
+    from . import batch as B
+    qs, ts = _cross_token_sides(queries, targets)
+    _, _, nearest, per_query = B.levenshtein_cross_tokens(qs, ts, _k(k), costs, cap=0, nearest=True, per_query=True)
+    words, counts = nearest.cpu().numpy().view("uint64"), per_query.cpu().numpy().view("uint32")
+    return [None if int(w) == 0xFFFFFFFFFFFFFFFF else (int(w) & 0xFFFFFFFF, int(w) >> 32, int(c)) for w, c in zip(words, counts)]
+
+
 def hamming_cross_many(queries, targets, k, upper=False):
     """Every query against every target in ONE device call (ta_hamming_cross): the sorted list of (q, t, d) with d =
     hamming(queries[q], targets[t]) for every pair of equal length where that is at most k; upper = True keeps only the pairs with t > q

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     # search over a batch of (needle, haystack) pairs (ta_search_batch.hip)
     "ta_levenshtein_search_batch", "ta_hamming_search_batch",
     # every query against every target (ta_cross.hip)
-    "ta_levenshtein_cross", "ta_hamming_cross", "ta_levenshtein_cross_with_opts",
+    "ta_levenshtein_cross", "ta_hamming_cross", "ta_levenshtein_cross_with_opts", "ta_levenshtein_cross_tokens",
     # every needle of a panel in every haystack (ta_cross.hip)
     "ta_levenshtein_search_cross", "ta_levenshtein_search_cross_with_opts", "ta_hamming_search_cross",
     "ta_hamming_search_cross_with_opts",
@@ -206,6 +206,7 @@ def lib():
     sig("ta_levenshtein_cross", i32, [sp, sz, sp, sz, u32, cp, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p])
     sig("ta_hamming_cross", i32, [sp, sz, sp, sz, u32, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("ta_levenshtein_cross_with_opts", i32, [sp, sz, sp, sz, u32, cp, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p])
+    sig("ta_levenshtein_cross_tokens", i32, [tp, sz, tp, sz, u32, cp, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("ta_levenshtein_search_cross", i32, [sp, sz, sp, sz, u32, cp, i32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     sig("ta_levenshtein_search_cross_with_opts", i32,
         [sp, sz, sp, sz, u32, cp, i32, u32, C.c_void_p, C.c_void_p, sz, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])

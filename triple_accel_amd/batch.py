@@ -205,9 +205,9 @@ def _token_values(t):
 
 class Tokens:
     """A batch side of 32-bit item sequences in HBM (Strings for token ids): CSR (values + n+1 int64 element offsets) or a fixed
-    (n, len) tensor.  No read slack is needed."""
+    (n, len) tensor.  No read slack is needed.  stride: the distance in items of two sequences of the strided form (default: length)."""
 
-    def __init__(self, values, off=None, length=0, max_len=0, n=None):
+    def __init__(self, values, off=None, length=0, max_len=0, n=None, stride=None):
         values = _token_values(values)
         assert values.is_cuda
         self.values, self.off, self.max_len = values, off, max_len
@@ -215,7 +215,14 @@ class Tokens:
             assert off.dtype == torch.int64 and off.is_cuda and off.is_contiguous()
             self.n, self.length, self.stride = off.numel() - 1, 0, 0
         else:
-            self.n, self.length, self.stride = n, length, length
+            self.n, self.length, self.stride = n, length, length if stride is None else stride
+
+    def __setattr__(self, name, value):
+        # the C view is built once per batch side (_ref); changing a field drops it
+        if name in ("values", "off", "stride", "length", "max_len"):
+            self.__dict__.pop("_cview", None)
+            self.__dict__.pop("_cref", None)
+        object.__setattr__(self, name, value)
 
     @classmethod
     def from_csr(cls, values, off, max_len=0):
@@ -588,6 +595,41 @@ def levenshtein_cross_with_opts(queries: Strings, targets: Strings, k, costs=LEV
                                                  hits.data_ptr() if cap else None, count.data_ptr(), cap,
                                                  None if nearest is None else nearest.data_ptr(),
                                                  None if per_query is None else per_query.data_ptr(), _stream())
+    if rc:
+        _raise(rc)
+    return hits, count, nearest, per_query
+
+
+def levenshtein_cross_tokens(queries: Tokens, targets: Tokens, k, costs=LEVENSHTEIN_COSTS, cap=None, hits=None, count=None, nearest=False,
+                             per_query=False, upper=False):
+    """levenshtein_cross_with_opts over token sequences, on the device (ta_levenshtein_cross_tokens): -> (hits, count, nearest, per_query).
+    The pair (q, t) is a hit with distance d exactly when levenshtein_k_batch_tokens answers d for it; hits, count, cap, nearest,
+    per_query, upper and the costs are levenshtein_cross_with_opts's (cross_to_arrays reads the result).  Queries of at most 64 tokens
+    (swap the sides when the short sequences are the targets: the distance is symmetric): a longer one raises NotImplementedError.  A
+    CSR side with max_len = 0 is measured by the library (one synchronisation).  Nothing else is synchronised: read count before
+    trusting hits."""
+    nq, nt, dev = queries.n, targets.n, targets.values.device
+    if cap is None:
+        cap = hits.numel() // 4 if hits is not None else min(nq * nt, max(1024, 8 * max(nq, nt)))
+    hits = torch.empty((cap, 4), dtype=torch.int32, device=dev) if hits is None else hits
+    count = torch.empty(1, dtype=torch.int64, device=dev) if count is None else count
+    if nearest is True:
+        nearest = torch.empty(nq, dtype=torch.int64, device=dev)
+    elif nearest is False:
+        nearest = None
+    if per_query is True:
+        per_query = torch.empty(nq, dtype=torch.int32, device=dev)
+    elif per_query is False:
+        per_query = None
+    assert hits.dtype == torch.int32 and hits.is_contiguous() and hits.numel() >= cap * 4
+    assert count.dtype == torch.int64 and count.numel() >= 1
+    assert nearest is None or (nearest.dtype == torch.int64 and nearest.is_contiguous() and nearest.numel() >= nq)
+    assert per_query is None or (per_query.dtype == torch.int32 and per_query.is_contiguous() and per_query.numel() >= nq)
+    cc = _costs(costs)._c()
+    rc = _n.lib().ta_levenshtein_cross_tokens(queries._ref(), nq, targets._ref(), nt, int(k), _C.byref(cc), _n.TA_CROSS_UPPER if upper else 0,
+                                              hits.data_ptr() if cap else None, count.data_ptr(), cap,
+                                              None if nearest is None else nearest.data_ptr(),
+                                              None if per_query is None else per_query.data_ptr(), _stream())
     if rc:
         _raise(rc)
     return hits, count, nearest, per_query

@@ -15,6 +15,32 @@
 
 namespace ta {
 
+// What a wavefront does with the 64 answers of query q (res: the unit distance of the lane's target t, 0xFFFFFFFF for no hit): the epilogue
+// of every walk (below; lev_cross_tok.hip)
+template <bool OPTS>
+__device__ __forceinline__ void lev_cross_emit(const CrossParams &P, uint32_t q, uint32_t t, uint32_t lane, uint32_t res, bool upper) {
+    bool hit = res != 0xFFFFFFFFu;
+    if (upper) hit = hit && t > q;
+    const unsigned long long mask = __ballot(hit);
+    if (!mask) return;
+    const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
+    unsigned long long base = 0;
+    if (lane == leader) {
+        base = atomicAdd(P.count, (unsigned long long)__popcll(mask));
+        if (OPTS && P.per_query) atomicAdd(P.per_query + q, (uint32_t)__popcll(mask));
+    }
+    base = ((unsigned long long)__builtin_amdgcn_readlane((uint32_t)(base >> 32), leader) << 32) |
+           __builtin_amdgcn_readlane((uint32_t)base, leader);
+    const unsigned long long idx = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
+    const uint32_t d = res * P.g;                                  // (g d <= k: no overflow)
+    if (hit && idx < P.cap) P.hits[idx] = ta_cross_hit{q, t, d, 0u};
+    if (P.nearest) {
+        const uint32_t dmin = ~DevWave::wave_max(hit ? ~res : 0u);
+        const unsigned long long best = __ballot(hit && res == dmin);
+        if (lane == (uint32_t)__ffsll((long long)best) - 1u) atomicMin(P.nearest + q, ((unsigned long long)d << 32) | t);
+    }
+}
+
 // OPTS: the call asks for TA_CROSS_UPPER or the per-query counts; without it the walk is ta_levenshtein_cross's as it always was
 template <class B, bool OPTS>
 __device__ __forceinline__ void lev_cross_walk(const CrossParams &P, uint8_t *tables) {
@@ -53,26 +79,7 @@ __device__ __forceinline__ void lev_cross_walk(const CrossParams &P, uint8_t *ta
         uint32_t res;
         bool skip;
         if (!B::query(lds, qp, m, tp, tl, live, first, P.k, res, skip)) continue;
-        bool hit = res != 0xFFFFFFFFu;
-        if (upper) hit = hit && t > q;
-        const unsigned long long mask = __ballot(hit);
-        if (!mask) continue;
-        const uint32_t leader = (uint32_t)__ffsll((long long)mask) - 1u;
-        unsigned long long base = 0;
-        if (lane == leader) {
-            base = atomicAdd(P.count, (unsigned long long)__popcll(mask));
-            if (OPTS && P.per_query) atomicAdd(P.per_query + q, (uint32_t)__popcll(mask));
-        }
-        base = ((unsigned long long)__builtin_amdgcn_readlane((uint32_t)(base >> 32), leader) << 32) |
-               __builtin_amdgcn_readlane((uint32_t)base, leader);
-        const unsigned long long idx = base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull));
-        const uint32_t d = res * P.g;                              // (g d <= k: no overflow)
-        if (hit && idx < P.cap) P.hits[idx] = ta_cross_hit{q, t, d, 0u};
-        if (P.nearest) {
-            const uint32_t dmin = ~DevWave::wave_max(hit ? ~res : 0u);
-            const unsigned long long best = __ballot(hit && res == dmin);
-            if (lane == (uint32_t)__ffsll((long long)best) - 1u) atomicMin(P.nearest + q, ((unsigned long long)d << 32) | t);
-        }
+        lev_cross_emit<OPTS>(P, q, t, lane, res, upper);
     }
 }
 

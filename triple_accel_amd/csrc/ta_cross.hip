@@ -1,7 +1,7 @@
-// ta_cross.hip -- ta_levenshtein_cross, ta_levenshtein_cross_with_opts, ta_hamming_cross, ta_levenshtein_search_cross,
+// ta_cross.hip -- ta_levenshtein_cross, ta_levenshtein_cross_with_opts, ta_levenshtein_cross_tokens, ta_hamming_cross, ta_levenshtein_search_cross,
 // ta_levenshtein_search_cross_with_opts, ta_hamming_search_cross and ta_hamming_search_cross_with_opts
-// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.19): validation, the length bounds, the query tile / the sub-batches and the launches of
-// lev_cross.hip / lev_cross_win.hip / ham_cross.hip / lev_search_cross.hip / lev_search_cross_w2.hip / ham_search_cross.hip /
+// (include/triple_accel_amd.h; DESIGN.md 3.13 - 3.20): validation, the length bounds, the query tile / the sub-batches and the launches of
+// lev_cross.hip / lev_cross_win.hip / lev_cross_tok.hip / ham_cross.hip / lev_search_cross.hip / lev_search_cross_w2.hip / ham_search_cross.hip /
 // ham_search_cross_w2.hip.  Everything is enqueued on the caller's stream; with every length bound given (strided sides, or CSR max_len)
 // there is no synchronisation and the call can be captured into a graph.  The shared host rules (cost check and scale, length bounds,
 // measured maxima) and the scratch slots' names (SLOT_CROSS_CTL, SLOT_SX_*) are those of ta_internal.h; the query tile's rule is
@@ -18,20 +18,26 @@ namespace ta {
 
 // the checks the cross entries share, in their order: counts, pointers and sizes, then the length bounds that are known without measuring
 // (max_query: the entry's limit on a query's length)
+// the two length limits' messages (tokens: the sides of ta_levenshtein_cross_tokens, lengths in items)
+static const char *cross_query_msg(uint32_t max_query, bool tokens) {
+    return tokens ? "cross: a query longer than 64 tokens" : max_query > 64 ? "cross: a query longer than 256 bytes" : "cross: a query longer than 64 bytes";
+}
+static const char *cross_target_msg(bool tokens) { return tokens ? "cross: a target of 2^32 tokens or more" : "cross: a target of 2^32 bytes or more"; }
+
 static int cross_check_args(const ta_strings *queries, size_t nq, const ta_strings *targets, size_t nt, const ta_cross_hit *hits_dev, size_t cap,
-                            uint32_t max_query = 64) {
+                            uint32_t max_query = 64, bool tokens = false) {
     if ((uint64_t)nq >> 32 || (uint64_t)nt >> 32) { set_last_error_msg("2^32 or more queries / targets"); return TA_ERR_ARG; }
-    if (nq && nt && (!queries->blob || !targets->blob)) { set_last_error_msg("null blob"); return TA_ERR_ARG; }
+    if (nq && nt && (!queries->blob || !targets->blob)) { set_last_error_msg(tokens ? "null data" : "null blob"); return TA_ERR_ARG; }
     if (cap && !hits_dev) { set_last_error_msg("cap > 0 with null hits_dev"); return TA_ERR_ARG; }
     if (cap > SIZE_MAX / sizeof(ta_cross_hit)) { set_last_error_msg("cap * sizeof(ta_cross_hit) overflows"); return TA_ERR_ARG; }
-    if (side_bound_known(queries) && side_bound(queries) > max_query) { set_last_error_msg(max_query > 64 ? "cross: a query longer than 256 bytes" : "cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
-    if (side_bound_known(targets) && side_bound(targets) >> 32) { set_last_error_msg("cross: a target of 2^32 bytes or more"); return TA_ERR_UNSUPPORTED; }
+    if (side_bound_known(queries) && side_bound(queries) > max_query) { set_last_error_msg(cross_query_msg(max_query, tokens)); return TA_ERR_UNSUPPORTED; }
+    if (side_bound_known(targets) && side_bound(targets) >> 32) { set_last_error_msg(cross_target_msg(tokens)); return TA_ERR_UNSUPPORTED; }
     return device_ready() ? TA_OK : TA_ERR_HIP;
 }
 
 // the longest query and target (measure_max_lens: one synchronisation where a CSR side gives no max_len), under the same two limits
 static int cross_max_lens(const ta_strings *qs, uint32_t nq, const ta_strings *ts, uint32_t nt, hipStream_t st, uint64_t *mq, uint64_t *mt,
-                          uint32_t max_query = 64) {
+                          uint32_t max_query = 64, bool tokens = false) {
     unsigned long long *dst = nullptr;
     if (!side_bound_known(qs) || !side_bound_known(ts)) {
         Scratch &c = tls_scratch(SLOT_CROSS_CTL);
@@ -39,8 +45,8 @@ static int cross_max_lens(const ta_strings *qs, uint32_t nq, const ta_strings *t
         dst = (unsigned long long *)c.dev;
     }
     if (int rc = measure_max_lens(qs, nq, ts, nt, dst, st, mq, mt)) return rc;
-    if (*mq > max_query) { set_last_error_msg(max_query > 64 ? "cross: a query longer than 256 bytes" : "cross: a query longer than 64 bytes"); return TA_ERR_UNSUPPORTED; }
-    if (*mt >> 32) { set_last_error_msg("cross: a target of 2^32 bytes or more"); return TA_ERR_UNSUPPORTED; }
+    if (*mq > max_query) { set_last_error_msg(cross_query_msg(max_query, tokens)); return TA_ERR_UNSUPPORTED; }
+    if (*mt >> 32) { set_last_error_msg(cross_target_msg(tokens)); return TA_ERR_UNSUPPORTED; }
     return TA_OK;
 }
 
@@ -139,6 +145,44 @@ extern "C" int ta_levenshtein_cross_with_opts(const ta_strings *queries, size_t 
     // P.k (3.17); TA_CROSS_FULL (tuning) takes the whole column instead.
     if (max_q <= 64) TA_HIP(lev_cross_launch(P, max_q <= 32 ? 1 : 2, trans, st));
     else TA_HIP(lev_cross_win_launch(P, env_int("TA_CROSS_FULL") ? (int)WIN_NB : win_ww(P.k), trans, st));
+    return TA_OK;
+}
+
+// The sides of a token call as the byte entries' host rules read them: the same five fields, every length, stride and offset in ITEMS
+// (measure_max_lens takes differences of offsets; a CSR side's `len`, the items `data` holds, plays no part here: side_bound reads max_len).
+static ta_strings tokens_as_side(const ta_tokens *t) { return ta_strings{(const uint8_t *)t->data, t->off, t->stride, t->len, t->max_len}; }
+
+extern "C" int ta_levenshtein_cross_tokens(const ta_tokens *queries, size_t nq, const ta_tokens *targets, size_t nt,
+                                           uint32_t k, const ta_edit_costs *costs, uint32_t flags,
+                                           ta_cross_hit *hits_dev, unsigned long long *count_dev, size_t cap,
+                                           uint64_t *nearest_dev, uint32_t *per_query_dev, void *stream) {
+    if (!queries || !targets || !costs || !count_dev) { set_last_error_msg("null queries / targets / costs / count_dev"); return TA_ERR_ARG; }
+    if (flags & ~TA_CROSS_UPPER) { set_last_error_msg("levenshtein cross tokens: unknown flag bits"); return TA_ERR_ARG; }
+    if (!costs_ok(costs)) return TA_ERR_BAD_COSTS;                                 // EditCosts::new, src/levenshtein.rs:44-52
+    const bool trans = costs->has_transpose != 0;
+    const uint32_t g = costs_scale(costs);                                         // LEVENSHTEIN_COSTS / RDAMERAU_COSTS: 1; g times one: g
+    if (!g) { set_last_error_msg("cross: unit-cost families and their multiples only"); return TA_ERR_UNSUPPORTED; }
+    const ta_strings qs = tokens_as_side(queries), ts = tokens_as_side(targets);
+    int rc = cross_check_args(&qs, nq, &ts, nt, hits_dev, cap, 64, true);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    StreamGuard guard(st);
+    // a measured query of more than 64 tokens is refused before any output is written, as ta_levenshtein_cross_with_opts does it
+    uint64_t max_q = 0, max_t = 0;
+    if (nq && nt && (rc = cross_max_lens(&qs, (uint32_t)nq, &ts, (uint32_t)nt, st, &max_q, &max_t, 64, true))) return rc;
+    if ((rc = cross_fill64(count_dev, 0u, 1, st))) return rc;
+    if (nearest_dev && (rc = cross_fill64((unsigned long long *)nearest_dev, 0xFFFFFFFFu, nq, st))) return rc;
+    if (per_query_dev && nq) TA_HIP(fill_u32_launch(per_query_dev, 0u, (uint32_t)nq, st));
+    if (nq == 0 || nt == 0) return TA_OK;
+
+    CrossParams P = {};
+    P.q = view_of(&qs); P.t = view_of(&ts);                                        // (items: lev_cross_tok.hip scales by four)
+    P.nq = (uint32_t)nq; P.nt = (uint32_t)nt;
+    P.k = k / g; P.g = g;
+    P.flags = flags;
+    P.hits = hits_dev; P.cap = cap; P.count = count_dev; P.nearest = (unsigned long long *)nearest_dev; P.per_query = per_query_dev;
+    P.qtile = cross_qtile(nq, nt, CROSS_MIN_QTILE, 1, env_int("TA_CROSS_QTILE"));   // ta_levenshtein_cross's tile
+    TA_HIP(lev_cross_tok_launch(P, max_q <= 32 ? 1 : 2, trans, st));
     return TA_OK;
 }
 

@@ -397,6 +397,9 @@ constexpr uint32_t CROSS_MIN_QTILE = 16;
 hipError_t lev_cross_launch(const CrossParams &P, int nw, bool trans, hipStream_t st);
 // queries of up to 256 bytes: a window of ww = 2, 3, 4 blocks of the column, or all 8 (ww >= win_ww(P.k), lev_cross_win_body.h)
 hipError_t lev_cross_win_launch(const CrossParams &P, int ww, bool trans, hipStream_t st);
+// ta_levenshtein_cross_tokens (lev_cross_tok.hip): P.q / P.t over 32-bit items -- blob = the first item; off, stride and len in ELEMENTS;
+// queries of at most 32 nw items
+hipError_t lev_cross_tok_launch(const CrossParams &P, int nw, bool trans, hipStream_t st);
 
 // ta_hamming_cross (ham_cross.hip): one lane per target, kept in nw dwords of registers; a wavefront walks a tile of queries, staged
 // through LDS a chunk of 256 / nw at a time
