@@ -41,7 +41,7 @@
 // 1.74e8 VALU instructions against 3.31e8 of lev_bits.hip, yet runs 0.72 ms against 0.53 ms: a wavefront keeps 256 pairs in
 // flight and touches every 128-byte line of its strings in four 32-byte pieces one epoch apart, far beyond what L2 holds,
 // so the fabric moves 3.1 GB for 516 MB of strings (0.41 ms with the loads taken out, 0.34 ms for the steps alone --
-// DESIGN.md 3.9).  Opt in with TA_FORCE_SLICED=1.
+// DESIGN.md 3.9).  Opt in with the force_sliced switch (lev_route.h: LevSwitches).
 #include "bit_transpose.h"
 #include "ta_internal.h"
 

@@ -186,7 +186,31 @@ static int side_max_len(const ta_strings *s, uint32_t n, hipStream_t st, uint64_
     return TA_OK;
 }
 
-// One k-bounded distance pass over the batch (or over `subset`); the heart of every distance entry point.
+// The switches of the distance path (lev_route.h: LevSwitches), one name per line; nothing else on that path reads these names.
+LevSwitches lev_switches() {
+    LevSwitches sw = {};
+    if (!g_tuning) return sw;
+    sw.no_bits = env_int("TA_NO_BITS") != 0;
+    sw.no_unit_scale = env_int("TA_NO_UNIT_SCALE") != 0;
+    sw.force_d = env_int("TA_FORCE_D");
+    sw.force_l = env_int("TA_FORCE_L");
+    sw.force_ch = env_int("TA_FORCE_CH");
+    sw.force_na = env_int("TA_FORCE_NA");
+    sw.bits_static = env_int("TA_BITS_STATIC");
+    sw.force_affine = env_int("TA_FORCE_AFFINE") != 0;
+    sw.force_trans_select = env_int("TA_FORCE_TRANS_SELECT") != 0;
+    sw.force_wide = env_int("TA_FORCE_WIDE") != 0;
+    sw.force_widebits = env_int("TA_FORCE_WIDEBITS");
+    sw.wb_no_tiles = env_int("TA_WB_NO_TILES") != 0;
+    sw.no_latency_rule = env_int("TA_NO_LATENCY_RULE") != 0;
+    sw.force_sliced = env_int("TA_FORCE_SLICED") != 0;
+    sw.no_one = env_int("TA_NO_ONE") != 0;
+    sw.no_bits2 = env_int("TA_NO_BITS2") != 0;
+    return sw;
+}
+
+// One k-bounded distance pass over the batch (or over `subset`); the heart of every distance entry point.  Which kernel it takes, with
+// what geometry, is lev_pass_route's answer (lev_route.h) to the facts gathered here; this function launches what the route names.
 // columns_ordered: `subset` lists the pairs by their exact column count (length_order_launch): 64 consecutive ones share it -- what
 // the VLINE form of the bit-parallel band kernel wants (one pass per wavefront)
 // n_dev (optional): the length of `subset` as a kernel before this pass left it on the device -- n_work is then its upper bound (grids,
@@ -194,142 +218,78 @@ static int side_max_len(const ta_strings *s, uint32_t n, hipStream_t st, uint64_
 int lev_pass(const ta_strings *a, const ta_strings *b, uint32_t n_work, const uint32_t *subset, uint32_t k,
              const ta_edit_costs *c, uint64_t max_len, uint32_t *out_dev, hipStream_t st, bool columns_ordered /* = false */,
              const uint32_t *n_dev /* = nullptr */) {
-    const uint32_t gc = c->gap_cost, sg = c->start_gap_cost;
     if (env_int("TA_FAIL_PASS")) { set_last_error_msg("TA_FAIL_PASS: a distance pass that fails (tests)"); return TA_ERR_UNSUPPORTED; }
-    // unit costs times g: the unit-cost kernels with k / g, then the answers times g (lev_plan.h: lev_unit_scale)
-    if (const uint32_t g = lev_unit_scale(c->mismatch_cost, gc, sg, c->has_transpose != 0, c->transpose_cost);
-        g && !env_int("TA_NO_BITS") && !env_int("TA_NO_UNIT_SCALE") && !env_int("TA_FORCE_D") && !env_int("TA_FORCE_L")) {
-        const ta_edit_costs uc = unit_costs(c->has_transpose != 0);
-        int rc = lev_pass(a, b, n_work, subset, k / g, &uc, max_len, out_dev, st, columns_ordered, n_dev);
-        if (rc) return rc;
-        TA_HIP(scale_results_launch(out_dev, subset, n_work, n_dev, g, st));
-        g_answer_single_store = false;                 // two stores to the result slot: the single-call path waits for the stream
-        ta_lev_select sel;
-        ta_levenshtein_select((size_t)max_len, (size_t)max_len, k, c, &sel);
-        g_last_launch.cell_bits = sel.cell_bits;       // (the reference's width class is that of the caller's costs and k)
-        return TA_OK;
-    }
-    LevPlan pl = lev_make_plan(k, c->mismatch_cost, gc, sg, max_len, env_int("TA_FORCE_D"), env_int("TA_FORCE_L"), env_int("TA_FORCE_CH"));
+    const LevSwitches sw = lev_switches();
+    const bool trans = c->has_transpose != 0;
     LevParams P;
     P.a = view_of(a); P.b = view_of(b);
-    P.subset = subset; P.trace = nullptr; P.out = out_dev; P.n = n_work; P.k = k;
-    P.mc = c->mismatch_cost; P.gc = gc; P.sg = sg; P.tc = c->has_transpose ? c->transpose_cost : 0;
-    P.u = pl.u; P.o = pl.o;
-    if (columns_ordered && subset) P.tune |= 4u;
-    if (n_dev) { P.n_dev = n_dev; P.tune |= 8u; }     // (tune bit 3: the grid of the upper bound, lev_bits.hip)
-    const bool affine = sg > 0 || env_int("TA_FORCE_AFFINE"), trans = c->has_transpose != 0;
-    ta_launch_info li = {};
-    li.band_offset = pl.o; li.affine = affine; li.transpose = trans;
-    g_answer_single_store = true;                     // every branch below is one launch except the tiled row-blocked form
-    ta_lev_select sel;
-    ta_levenshtein_select((size_t)max_len, (size_t)max_len, k, c, &sel);
-    li.cell_bits = sel.cell_bits;
-    // unit-cost families (levenshtein(), rdamerau(), levenshtein_simd_k(), the exp loop) have bit-parallel kernels
-    const uint32_t tcost = c->has_transpose ? c->transpose_cost : 0;
-    const LevBitsPlan bp = lev_bits_make_plan(k, c->mismatch_cost, gc, sg, trans, tcost, max_len, env_int("TA_FORCE_NA"), env_int("TA_FORCE_CH"),
-                                              env_int("TA_BITS_STATIC"));
-    const bool dp_forced = env_int("TA_NO_BITS") || env_int("TA_FORCE_D") || env_int("TA_FORCE_L") || env_int("TA_FORCE_AFFINE") ||
-                           env_int("TA_FORCE_TRANS_SELECT") || env_int("TA_FORCE_WIDE");
-    // a pass of few pairs is as slow as its slowest wavefront: the chooser then compares wavefronts, not pairs (lev_plan.h);
-    // the switches that pin a kernel layout keep the throughput choice
-    const bool pinned = env_int("TA_NO_LATENCY_RULE") || env_int("TA_FORCE_NA") || env_int("TA_BITS_STATIC") || env_int("TA_FORCE_CH") ||
-                        env_int("TA_FORCE_SLICED");
-    LevChoice ch = lev_choose(k, c->mismatch_cost, gc, sg, trans, tcost, max_len, dp_forced, pinned ? 0xFFFFFFFFu : n_work);
-    const bool unit = costs_unit(c);
-    // a handful of long fixed-length pairs: the tiled row-blocked form uses many wavefronts per pair, whatever the band
-    if (unit && !dp_forced && ch.kernel != LEV_K_BITS && (n_work == 1 || (n_work <= 16 && !subset)) && !a->off && !b->off &&
-        (a->len < b->len ? a->len : b->len) > 2ull * 4096ull && !env_int("TA_WB_NO_TILES")) {
-        ch.kernel = LEV_K_WIDEBITS;
-        ch.rows_per_lane = 64;
-    }
-    if (env_int("TA_FORCE_WIDEBITS") && unit && !dp_forced) {
-        ch.kernel = LEV_K_WIDEBITS;
-        ch.rows_per_lane = env_int("TA_FORCE_WIDEBITS") == 64 ? 64 : 32;
-    }
-    // fixed-length batches with a band of 25..45 diagonals: 32 pairs per register, three band cells per lane (lev_sliced.hip);
-    // opt-in -- fewer instructions than the bit-parallel band kernel but bound by the refetch of its string lines
+    LevPassFacts F = {};
+    F.n_work = n_work; F.subset = subset != nullptr; F.n_dev = n_dev != nullptr; F.columns_ordered = columns_ordered;
+    F.a_csr = a->off != nullptr; F.b_csr = b->off != nullptr; F.a_len = a->len; F.b_len = b->len;
+    F.max_len = max_len; F.k = k; F.c = costs_of(c);
 #ifdef TA_EXPERIMENTAL
-    uint32_t sl_strips = 0;
-    const bool sliced = ch.kernel == LEV_K_BITS && unit && !trans && !subset && !dp_forced && env_int("TA_FORCE_SLICED") &&
-                        lev_sliced_applies(P.a, P.b, bp.u, &sl_strips);
-    if (sliced) {
-        uint32_t grid = 0, lds = 0, ppw = 0;
-        TA_HIP(lev_sliced_launch(P.a, P.b, n_work, k, bp.u, out_dev, st, &grid, &lds, &ppw));
-        li.kernel = 5; li.diags_per_lane = 3; li.lanes_per_pair = sl_strips; li.pairs_per_wave = ppw;
-        li.grid = grid; li.lds_bytes = lds; li.band_offset = 0;
-        if (env_int("TA_DEBUG")) fprintf(stderr, "[triple_accel_amd] lev pass: n=%u k=%u u=%u kernel=5 (pair-sliced) grid=%u lds=%u\n", n_work, k, bp.u, grid, lds);
-        g_last_launch = li;
-        return TA_OK;                                  // (like the single-pair branch below: nothing else may write `out`)
+    if (const uint32_t g = costs_scale(c); sw.force_sliced && g) {      // (the band of the unit-cost pass: k / g)
+        uint32_t strips = 0;
+        if (lev_sliced_applies(P.a, P.b, lev_batch_unit_k(k / g, 1, 1, 0, max_len), &strips)) F.sliced_strips = strips;
     }
 #endif
-    uint32_t u_one = 0;
-    if (n_work == 1 && !dp_forced && !pinned && !env_int("TA_FORCE_WIDEBITS") && !env_int("TA_NO_ONE") &&
-        lev_one_applies(k, c->mismatch_cost, gc, sg, trans, tcost, max_len, &u_one)) {
-        // a lone pair with a band of up to 64 diagonals: match vectors 64 columns at a time, the recurrence on the scalar unit
-        P.u = u_one; P.o = 0; P.L = 64; P.PW = 1; P.lds_per_wave = 0; P.Tw = 0; P.ch = 0;
-        uint32_t lds = 0;
-        TA_HIP(lev_one_launch(P, trans, max_len, st, &lds));
-        li.kernel = 6; li.diags_per_lane = 64; li.lanes_per_pair = 64; li.pairs_per_wave = 1;
-        li.grid = 1; li.lds_bytes = lds; li.band_offset = 0;
-        if (env_int("TA_DEBUG")) fprintf(stderr, "[triple_accel_amd] lev pass: n=1 k=%u u=%u kernel=6 (single pair, scalar-unit recurrence) lds=%u\n", k, u_one, lds);
-        g_last_launch = li;
-        return TA_OK;
-    }
-    const LevBits2Plan b2 = lev_bits2_make_plan(k, c->mismatch_cost, gc, sg, trans, tcost, max_len, !a->off && !b->off, n_work);
-    if (ch.kernel == LEV_K_BITS && b2.ok && !pinned && !env_int("TA_NO_BITS2")) {
-        // narrow band, big fixed-length batch: two pairs per lane share the recurrence AND the byte test (lev_bits2_body.h, the
-        // stride-8 window with both pairs' bytes in every register): 27 % fewer instructions per pair, 16 wavefronts per CU;
-        // cfg4 0.118 against 0.135 ms (profiles/r03/ab_band_kernel.md).  TA_NO_BITS2=1 keeps one pair per lane.
-        P.u = b2.u; P.o = 0; P.L = 1; P.PW = 128; P.lds_per_wave = b2.lds_per_wave; P.Tw = b2.Tw; P.ch = 64;
-        uint32_t grid = 0, lds = 0;
-        TA_HIP(lev_bits2_launch(P, b2, trans, st, &grid, &lds));
-        li.kernel = 3; li.diags_per_lane = 15; li.lanes_per_pair = 1; li.pairs_per_wave = 128;
-        li.grid = grid; li.lds_bytes = lds; li.band_offset = 0;
-    } else if (ch.kernel == LEV_K_BITS) {
-        P.u = bp.u; P.o = 0; P.L = 1; P.PW = 64; P.lds_per_wave = bp.lds_per_wave; P.Tw = bp.Tw; P.ch = bp.ch;
-        uint32_t grid = 0, lds = 0;
-        TA_HIP(lev_bits_launch(P, bp, trans, max_len, st, &grid, &lds));
-        li.kernel = 3; li.diags_per_lane = bp.s8 ? 33u : 4u * (uint32_t)bp.NA; li.lanes_per_pair = 1; li.pairs_per_wave = 64;
-        li.grid = grid; li.lds_bytes = lds; li.band_offset = 0;
-    } else if (ch.kernel == LEV_K_WIDEBITS && (n_work == 1 || (n_work <= 16 && !subset)) && !a->off && !b->off &&
-               a->len <= 0xFFFFFFF0ull && b->len <= 0xFFFFFFF0ull &&
-               (a->len < b->len ? a->len : b->len) > 2ull * 64ull * (uint64_t)ch.rows_per_lane &&
-               (a->len > b->len ? a->len - b->len : b->len - a->len) <= bp.u && !env_int("TA_WB_NO_TILES")) {
-        // ONE long pair (the single-call API) or a handful of them (fixed-length batch): a pair's stripe sweeps are cut into
-        // tiles and spread over many wavefronts, pair after pair
-        uint32_t launches = 0;
-        g_answer_single_store = false;                 // many launches per pair; only the last tile stores the answer
+    const LevPassRoute R = lev_pass_route(F, sw);
+    // unit costs times g: the unit-cost kernels with k / g, then the answers times g (lev_plan.h: lev_unit_scale)
+    const ta_edit_costs uc = unit_costs(trans);
+    if (R.scale) { c = &uc; k /= R.scale; }
+    P.subset = subset; P.trace = nullptr; P.out = out_dev; P.n = n_work; P.k = k;
+    P.mc = c->mismatch_cost; P.gc = c->gap_cost; P.sg = c->start_gap_cost; P.tc = trans ? c->transpose_cost : 0;
+    P.u = R.u; P.o = R.o; P.L = R.L; P.PW = R.PW; P.lds_per_wave = R.lds_per_wave; P.Tw = R.Tw; P.ch = R.ch;
+    P.tune = R.tune; P.n_dev = n_dev;
+    ta_launch_info li = {};
+    li.kernel = R.info.kernel; li.diags_per_lane = R.info.diags_per_lane; li.lanes_per_pair = R.info.lanes_per_pair;
+    li.pairs_per_wave = R.info.pairs_per_wave; li.band_offset = R.info.band_offset; li.cell_bits = R.info.cell_bits;
+    li.affine = R.info.affine; li.transpose = R.info.transpose;
+    switch (R.kind) {
+    case LEV_PASS_SLICED:
+#ifdef TA_EXPERIMENTAL
+        TA_HIP(lev_sliced_launch(P.a, P.b, n_work, k, R.bp.u, out_dev, st, &li.grid, &li.lds_bytes, &li.pairs_per_wave));
+        break;
+#else
+        return TA_ERR_UNSUPPORTED;                     // (the route names it in TA_EXPERIMENTAL builds only)
+#endif
+    case LEV_PASS_ONE:
+        TA_HIP(lev_one_launch(P, trans, max_len, st, &li.lds_bytes));
+        li.grid = 1;
+        break;
+    case LEV_PASS_BITS2:
+        TA_HIP(lev_bits2_launch(P, R.b2, trans, st, &li.grid, &li.lds_bytes));
+        break;
+    case LEV_PASS_BITS:
+        TA_HIP(lev_bits_launch(P, R.bp, trans, max_len, st, &li.grid, &li.lds_bytes));
+        break;
+    case LEV_PASS_HUGE:                                // pair after pair; li.grid: the launches of a pair
         for (uint32_t p = 0; p < n_work; p++)
             TA_HIP(lev_widebits_huge_launch(a->blob + (uint64_t)p * a->stride, (uint32_t)a->len, b->blob + (uint64_t)p * b->stride,
-                                            (uint32_t)b->len, bp.u, k, ch.rows_per_lane, trans, out_dev + p, st, &launches));
-        li.kernel = 4; li.diags_per_lane = (uint32_t)ch.rows_per_lane; li.lanes_per_pair = 64; li.pairs_per_wave = 1;
-        li.grid = launches; li.lds_bytes = 0; li.band_offset = 0;
-    } else if (ch.kernel == LEV_K_WIDEBITS) {
-        P.u = bp.u; P.o = 0; P.L = 64; P.PW = 1; P.lds_per_wave = 0; P.Tw = 0; P.ch = 0;
-        uint32_t grid = 0, lds = 0;
-        TA_HIP(lev_widebits_launch(P, ch.rows_per_lane, max_len, trans, st, &grid, &lds));
-        li.kernel = 4; li.diags_per_lane = (uint32_t)ch.rows_per_lane; li.lanes_per_pair = 64; li.pairs_per_wave = 1;
-        li.grid = grid; li.lds_bytes = lds; li.band_offset = 0;
-    } else if (pl.ok && !env_int("TA_FORCE_WIDE")) {
-        P.L = pl.L; P.PW = pl.PW; P.lds_per_wave = pl.lds_per_wave; P.Tw = pl.Tw; P.ch = pl.ch;
-        uint32_t grid = 0, lds = 0;
-        const int tmode = !trans ? 0 : ((2u * P.mc <= 255u + P.tc && !env_int("TA_FORCE_TRANS_SELECT")) ? 1 : 2);
-        TA_HIP(lev_band_launch(P, pl, affine, tmode, st, &grid, &lds));
-        li.kernel = 1; li.diags_per_lane = pl.D; li.lanes_per_pair = pl.L; li.pairs_per_wave = pl.PW;
-        li.grid = grid; li.lds_bytes = lds;
-    } else {
-        P.L = 0; P.PW = 1; P.Tw = 0;
-        P.lds_per_wave = (uint32_t)((max_len + 2 > 0xFFFFFFF0ull) ? 0xFFFFFFF0ull : max_len + 2);   // boundary line length
-        uint32_t grid = 0, lds = 0, threads = 0, dpt = 0;
-        TA_HIP(lev_wide_launch(P, trans, st, &grid, &lds, &threads, &dpt));
-        li.kernel = 2; li.diags_per_lane = dpt; li.lanes_per_pair = threads; li.pairs_per_wave = 0;
-        li.grid = grid; li.lds_bytes = lds; li.affine = 1;
+                                            (uint32_t)b->len, R.bp.u, k, R.rows_per_lane, trans, out_dev + p, st, &li.grid));
+        break;
+    case LEV_PASS_ROWS:
+        TA_HIP(lev_widebits_launch(P, R.rows_per_lane, max_len, trans, st, &li.grid, &li.lds_bytes));
+        break;
+    case LEV_PASS_BAND:
+        TA_HIP(lev_band_launch(P, R.pl, R.affine, R.tmode, st, &li.grid, &li.lds_bytes));
+        break;
+    case LEV_PASS_WIDE:
+        TA_HIP(lev_wide_launch(P, trans, st, &li.grid, &li.lds_bytes, &li.lanes_per_pair, &li.diags_per_lane));
+        break;
     }
-    if (env_int("TA_DEBUG"))
-        fprintf(stderr, "[triple_accel_amd] lev pass: n=%u k=%u u=%u kernel=%u D=%u L=%u pairs/wave=%u width=%u-bit grid=%u lds=%u\n",
-                n_work, k, pl.u, li.kernel, li.diags_per_lane, li.lanes_per_pair, li.pairs_per_wave, li.cell_bits, li.grid,
-                li.lds_bytes);
+    if (R.scale) TA_HIP(scale_results_launch(out_dev, subset, n_work, n_dev, R.scale, st));
     g_last_launch = li;
+    g_answer_single_store = R.single_store;
+    if (!env_int("TA_DEBUG")) return TA_OK;
+    if (R.kind == LEV_PASS_SLICED)
+        fprintf(stderr, "[triple_accel_amd] lev pass: n=%u k=%u u=%u kernel=5 (pair-sliced) grid=%u lds=%u\n", n_work, k, R.bp.u, li.grid, li.lds_bytes);
+    else if (R.kind == LEV_PASS_ONE)
+        fprintf(stderr, "[triple_accel_amd] lev pass: n=1 k=%u u=%u kernel=6 (single pair, scalar-unit recurrence) lds=%u\n", k, R.u, li.lds_bytes);
+    else
+        fprintf(stderr, "[triple_accel_amd] lev pass: n=%u k=%u u=%u kernel=%u D=%u L=%u pairs/wave=%u width=%u-bit grid=%u lds=%u\n",
+                n_work, k, R.pl.u, li.kernel, li.diags_per_lane, li.lanes_per_pair, li.pairs_per_wave, li.cell_bits, li.grid,
+                li.lds_bytes);
     return TA_OK;
 }
 
@@ -450,22 +410,8 @@ int ta_edit_costs_check_search(const ta_edit_costs *c) {   // src/levenshtein.rs
 int ta_levenshtein_select(size_t a_len, size_t b_len, uint32_t k, const ta_edit_costs *c, ta_lev_select *out) {
     if (!c || !out) return TA_ERR_ARG;
     if (!costs_ok(c)) return TA_ERR_BAD_COSTS;
-    const uint32_t mn = (uint32_t)(a_len < b_len ? a_len : b_len), mx = (uint32_t)(a_len < b_len ? b_len : a_len);
-    const uint32_t mc = c->mismatch_cost, gc = c->gap_cost, sg = c->start_gap_cost;
-    uint32_t sub_all = mn * mc;
-    uint32_t gaps_all = (mn << 1) * gc + (mn == 0 ? 0u : sg + (mx == mn ? sg : 0u));
-    uint32_t bound = (sub_all < gaps_all ? sub_all : gaps_all) + (mx - mn) * gc + (mx == mn ? 0u : sg);
-    uint32_t max_k = k < bound ? k : bound;
-    uint32_t unit_k = lev_sat_sub(max_k, sg) / gc;
-    if (unit_k > mx) unit_k = mx;
-    out->max_k = max_k; out->unit_k = unit_k;
-    out->cell_bits = 32; out->ref_lanes = 0;
-    static const uint32_t ub[4] = {32, 64, 128, 256};
-    if (max_k <= 254u) {
-        for (int t = 0; t < 4; t++)
-            if (unit_k <= ub[t] - 2) { out->cell_bits = 8; out->ref_lanes = ub[t]; return TA_OK; }
-    }
-    if (max_k <= 65534u) out->cell_bits = 16;
+    const LevSelect s = lev_select(a_len, b_len, k, c->mismatch_cost, c->gap_cost, c->start_gap_cost);     // lev_route.h
+    out->max_k = s.max_k; out->unit_k = s.unit_k; out->cell_bits = s.cell_bits; out->ref_lanes = s.ref_lanes;
     return TA_OK;
 }
 
@@ -510,20 +456,21 @@ int ta_levenshtein_k_batch(const ta_strings *a, const ta_strings *b, size_t n, u
     // every wavefront then sees pairs within 8 bytes of each other.  TA_NO_LENGTH_ORDER=1 keeps the batch order.
     const uint32_t *order = nullptr;
     bool exact_columns = false;
+    const LevSwitches sw = lev_switches();
     if (lev_wants_length_order(a->off || b->off, n, max_len) && !env_int("TA_NO_LENGTH_ORDER")) {
         const uint32_t u = lev_batch_unit_k(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, max_len);
         // the key counts what the kernel of this pass iterates over: columns (bit-parallel kernels) or anti-diagonal steps (DP band kernel).
         // (the kernels whose time follows max(len_a, len_b) or len_a -- two pairs per lane, the single-pair kernel, the row-blocked
         // one -- never see a length-ordered CSR wavefront of many pairs: the first takes fixed-length batches only, the other two run ONE pair
         // per wavefront, where the order only shapes the launch's tail; len_b is the right key for everything that is ordered by columns.)
-        const bool by_steps = !costs_scale(costs) || env_int("TA_NO_BITS") || env_int("TA_FORCE_D") || env_int("TA_FORCE_L");
+        const bool by_steps = !costs_scale(costs) || sw.unit_off();
         if ((rc = order_pairs(a, b, (uint32_t)n, u, max_len, by_steps, env_int("TA_BITS_VLINE") != 0, SLOT_ORDER, SLOT_ORDER_BINS, st, &order, &exact_columns))) return rc;
     }
     // TA_OPT_UNIT_PREFILTER (an option, off by default: the work then depends on the data): a weighted batch first runs the UNIT-cost
     // bit-parallel band pass with k' = lev_unit_filter_k -- "unit distance > k'" implies "weighted distance > k", i.e. None
     // (src/levenshtein.rs:539-541) -- and the DP band kernel prices only the pairs that pass answered (a list whose length stays on the
     // device).  Dissimilar batches cost the unit pass alone; a batch of near pairs pays for both.
-    if (unit_prefilter_enabled() && n >= 1024 && !env_int("TA_NO_BITS") && !env_int("TA_FORCE_D") && !env_int("TA_FORCE_L")) {
+    if (unit_prefilter_enabled() && n >= 1024 && !sw.unit_off()) {
         const bool trans = costs->has_transpose != 0;
         const uint32_t kf = lev_unit_filter_k(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, trans, costs->transpose_cost);
         if (!costs_scale(costs) && kf != 0xFFFFFFFFu && lev_choose(kf, 1, 1, 0, trans, trans ? 1u : 0u, max_len, false, (uint32_t)n).kernel == LEV_K_BITS) {
@@ -560,7 +507,8 @@ int ta_levenshtein_k_batch_alphabet(const ta_strings *a, const ta_strings *b, si
     const bool trans = costs->has_transpose != 0;
     const uint64_t max_len = fixed ? (a->len > b->len ? a->len : b->len) : 0;
     uint32_t u = 0, q_shift = 0, q_table = 0, q_memb = 0, q_hi = 0;
-    const bool pinned = env_int("TA_NO_BITS") || env_int("TA_FORCE_NA") || env_int("TA_BITS_STATIC") || env_int("TA_FORCE_D") || env_int("TA_NO_BITSQ");
+    const LevSwitches sw = lev_switches();
+    const bool pinned = sw.no_bits || sw.force_na || sw.bits_static || sw.force_d || env_int("TA_NO_BITSQ");
     if (!fixed || pinned || !alphabet ||
         !lev_bitsq_applies(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, trans, trans ? costs->transpose_cost : 0, max_len, true, n, &u) ||
         alphabet_len == 0)
@@ -653,27 +601,21 @@ int ta_levenshtein_exp_batch(const ta_strings *a, const ta_strings *b, size_t n,
     g_exp_passes = 0;
     uint32_t *sub_in = nullptr, *bufs[2] = {(uint32_t *)s0.dev, (uint32_t *)s1.dev};
     uint32_t n_left = (uint32_t)n;                          // unresolved pairs (sub_in == nullptr: all of them)
-    uint32_t k = 30;                                        // src/levenshtein.rs:1446, 1486, 1517
-    // The FIRST threshold as wide as the cheapest kernel's window: the stride-8 form holds 33 diagonals whatever k <= 32 asks for (31 with the
-    // transposition term's two extra ones: k = 30), so unit costs start at k = 32 (g x unit costs: 32 g) for the price of 30 -- a pair at distance
-    // 31 or 32 is answered by the first round instead of the 61-diagonal one (cfg3 on similar strings: 32 substitutions per pair; 2.29 -> 0.9 ms per
-    // 100K pairs).  levenshtein_exp returns the distance: any schedule of thresholds finds the same value (:1445-1454); from the second round on
-    // the reference's 60, 120, ... stand.  TA_EXP_FAITHFUL=1 keeps 30.
-    uint32_t k_first = 30;
-    if (!env_int("TA_EXP_FAITHFUL") && !costs->has_transpose && costs->start_gap_cost == 0 && costs->mismatch_cost == costs->gap_cost)
-        k_first = 32u * costs->gap_cost;                    // (gap_cost <= 255: no overflow)
-    k = k_first;
+    // the threshold schedule (lev_route.h: lev_exp_first_k, lev_exp_finish_now, lev_exp_next_k), the same for both loops below
+    const LevSwitches sw = lev_switches();
+    const LevCosts lc = costs_of(costs);
+    const bool dpo = sw.no_bits, faithful = env_int("TA_EXP_FAITHFUL") != 0;
+    const uint32_t k_first = lev_exp_first_k(lc, faithful);
+    uint32_t k = k_first;
     // ragged (CSR) batches: the rounds take their pairs in length order, as ta_levenshtein_k_batch does (the list of the still
     // unresolved pairs is compacted from the ordered one, which keeps it ordered block by block)
     if (lev_wants_length_order(a->off || b->off, n, max_len) && !env_int("TA_NO_LENGTH_ORDER")) {
         const uint32_t u0 = lev_batch_unit_k(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, max_len);
         const uint32_t *ordered = nullptr;
-        if ((rc = order_pairs(a, b, (uint32_t)n, u0, max_len, !costs_scale(costs) || env_int("TA_NO_BITS"), false, SLOT_ORDER, SLOT_ORDER_BINS, st, &ordered, nullptr))) return rc;
+        if ((rc = order_pairs(a, b, (uint32_t)n, u0, max_len, !costs_scale(costs) || sw.no_bits, false, SLOT_ORDER, SLOT_ORDER_BINS, st, &ordered, nullptr))) return rc;
         sub_in = (uint32_t *)ordered;
     }
     int flip = 0;
-    const uint32_t tcx = costs->has_transpose ? costs->transpose_cost : 0;
-    const bool dpo = env_int("TA_NO_BITS") != 0, faithful = env_int("TA_EXP_FAITHFUL") != 0;
     // Big batches: the rounds are DEVICE-DRIVEN -- every list (the pairs a round works on, the pairs it leaves unresolved) carries its
     // length in a device counter that the next kernel reads, every launch is sized for the list's upper bound (the batch) and the
     // wavefronts behind its end leave at once: the whole k schedule is enqueued without a host round trip between rounds, the call
@@ -688,11 +630,7 @@ int ta_levenshtein_exp_batch(const ta_strings *a, const ta_strings *b, size_t n,
         uint32_t *counters = (uint32_t *)cnt.dev;
         const uint32_t *n_in_dev = nullptr;                 // the length of sub_in (nullptr: n, exactly)
         for (int round = 0; round < MAX_ROUNDS; round++) {
-            if (!faithful && k != 0xFFFFFFFFu) {
-                const double c_this = lev_choose(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose != 0, tcx, max_len, dpo, (uint32_t)n).cost;
-                const double c_full = lev_choose(0xFFFFFFFFu, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose != 0, tcx, max_len, dpo, (uint32_t)n).cost;
-                if (c_this > 0.25 * c_full) k = 0xFFFFFFFFu;
-            }
+            if (k != 0xFFFFFFFFu && lev_exp_finish_now(k, lc, max_len, dpo, (uint32_t)n)) k = 0xFFFFFFFFu;
             const uint32_t *work = sub_in, *work_n_dev = n_in_dev;
             if (bounded && k != 0xFFFFFFFFu) {
                 TA_HIP(compact_bound_launch(out_dev, (const uint32_t *)bnd.dev, k, sub_in, (uint32_t)n, n_in_dev, (uint32_t *)wrk.dev, counters + 2 * round, st));
@@ -707,20 +645,13 @@ int ta_levenshtein_exp_batch(const ta_strings *a, const ta_strings *b, size_t n,
             sub_in = bufs[flip];
             n_in_dev = counters + 2 * round + 1;
             flip ^= 1;
-            k = (k > 0x7FFFFFFFu) ? 0xFFFFFFFFu : (round == 0 && k == k_first && k_first != 30u ? 60u * costs->gap_cost : k * 2);    // k *= 2 (:1452); saturate instead of wrapping
+            k = lev_exp_next_k(k, round, k_first, lc.gc);
         }
         g_answer_single_store = false;
         return TA_OK;
     }
     for (int round = 0; round < 40 && n_left > 0; round++) {
-        // Once a bounded pass would cost more than a quarter of the unbounded one (kernel cost model, lev_plan.h: per pair for
-        // big passes, per wavefront for small ones), it is cheaper in expectation to finish the unresolved pairs with
-        // k = u32::MAX right away (same return values -- levenshtein_exp returns the distance, whatever k schedule finds it).
-        if (!faithful && k != 0xFFFFFFFFu) {
-            const double c_this = lev_choose(k, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose != 0, tcx, max_len, dpo, n_left).cost;
-            const double c_full = lev_choose(0xFFFFFFFFu, costs->mismatch_cost, costs->gap_cost, costs->start_gap_cost, costs->has_transpose != 0, tcx, max_len, dpo, n_left).cost;
-            if (c_this > 0.25 * c_full) k = 0xFFFFFFFFu;
-        }
+        if (!faithful && k != 0xFFFFFFFFu && lev_exp_finish_now(k, lc, max_len, dpo, n_left)) k = 0xFFFFFFFFu;
         const uint32_t *work = sub_in;
         uint32_t n_work = n_left;
         if (bounded && k != 0xFFFFFFFFu) {
@@ -746,7 +677,7 @@ int ta_levenshtein_exp_batch(const ta_strings *a, const ta_strings *b, size_t n,
             flip ^= 1;
             n_left = left;
         }
-        k = (k > 0x7FFFFFFFu) ? 0xFFFFFFFFu : (round == 0 && k == k_first && k_first != 30u ? 60u * costs->gap_cost : k * 2);        // k *= 2 (:1452); saturate instead of wrapping
+        k = lev_exp_next_k(k, round, k_first, lc.gc);
     }
     return TA_OK;
 }

@@ -10,6 +10,7 @@
 #include "../../include/triple_accel_amd.h"
 #include "lev_band_body.h"
 #include "lev_plan.h"
+#include "lev_route.h"
 
 namespace ta {
 
@@ -120,10 +121,11 @@ static inline ta_strings strings_slice(const ta_strings *s, uint64_t lo, uint64_
 static inline ta_edit_costs unit_costs(bool trans) {       // LEVENSHTEIN_COSTS, or RDAMERAU_COSTS with the transposition term
     return ta_edit_costs{1, 1, 0, (uint8_t)(trans ? 1 : 0), (uint8_t)(trans ? 1 : 0)};
 }
+static inline LevCosts costs_of(const ta_edit_costs *c) {   // as the planners take them: no transposition, no cost
+    return LevCosts{c->mismatch_cost, c->gap_cost, c->start_gap_cost, c->has_transpose != 0, c->has_transpose ? (uint32_t)c->transpose_cost : 0u};
+}
 static inline uint32_t launch_cell_bits(uint64_t max_len, uint32_t k, const ta_edit_costs *c) {   // ta_launch_info.cell_bits of a batch
-    ta_lev_select sel;
-    ta_levenshtein_select((size_t)max_len, (size_t)max_len, k, c, &sel);
-    return sel.cell_bits;
+    return lev_select(max_len, max_len, k, c->mismatch_cost, c->gap_cost, c->start_gap_cost).cell_bits;
 }
 // the length bound of a batch side: known without measuring (strided, or CSR with max_len given), and its value
 static inline bool side_bound_known(const ta_strings *s) { return !s->off || s->max_len; }
@@ -188,6 +190,8 @@ struct StreamGuard {
 bool tuning_enabled();
 const char *env_str(const char *name);
 int env_int(const char *name);
+// the switches of the distance path (lev_route.h), read in this one place; all clear at once without TA_TUNING
+LevSwitches lev_switches();
 
 // The table form's host rule (its pure half: lev_bits_tab_applies, lev_plan.h): a launch of the stride-8 line form without transposition
 // term, checkpoints, early out or a device-side pair count, of at least LEV_BITS_TAB_MIN_PAIRS pairs.  Under TA_TUNING,

@@ -144,9 +144,10 @@ static int trace_batch_impl(const ta_strings *a, const ta_strings *b, size_t n, 
     if (packed_dev && (max_len >= (1ull << 29) || cap > 0xFFFFFFFFull)) { set_last_error_msg("packed tracebacks: strings of 2^29 bytes and more"); return TA_ERR_UNSUPPORTED; }
     // Unit costs times g (lev_unit_scale): every alignment costs g times its unit cost, every comparison of the recurrence and of the walk
     // keeps its outcome -- the script IS the unit-cost script for k / g, the distance g times the unit one (3.4c): the checkpoint kernel
-    // serves EditCosts(g, g, 0, None | Some(g)) too.  TA_NO_UNIT_SCALE=1 keeps the DP band kernel's records.
+    // serves EditCosts(g, g, 0, None | Some(g)) too.  The no_unit_scale switch (lev_route.h: LevSwitches) keeps the DP band kernel's records.
+    const LevSwitches sw = lev_switches();
     if (const uint32_t g = lev_unit_scale(costs->mismatch_cost, gc, sg, costs->has_transpose != 0, costs->transpose_cost);
-        g && !env_int("TA_NO_BITS") && !env_int("TA_NO_UNIT_SCALE") && !env_int("TA_TRACE_NO_BITS")) {
+        g && !sw.no_bits && !sw.no_unit_scale && !env_int("TA_TRACE_NO_BITS")) {
         const bool tr = costs->has_transpose != 0;
         const uint32_t uu = lev_batch_unit_k(k / g, 1, 1, 0, max_len);
         if ((uint64_t)uu + 1u + (tr ? 2u : 0u) <= 33u && max_len < (1ull << 29)) {
@@ -164,7 +165,7 @@ static int trace_batch_impl(const ta_strings *a, const ta_strings *b, size_t n, 
     {
         const bool trans = costs->has_transpose != 0;
         const uint32_t u = lev_batch_unit_k(k, 1, 1, 0, max_len);
-        if (costs_unit(costs) && (uint64_t)u + 1u + (trans ? 2u : 0u) <= 33u && max_len < (1ull << 29) /* a run's count has 29 bits */ && !env_int("TA_TRACE_NO_BITS") && !env_int("TA_NO_BITS")) {
+        if (costs_unit(costs) && (uint64_t)u + 1u + (trans ? 2u : 0u) <= 33u && max_len < (1ull << 29) /* a run's count has 29 bits */ && !env_int("TA_TRACE_NO_BITS") && !sw.no_bits) {
             // The kernel indexes its run lists with 32 bits (pair slot x runs_cap) and its scratch -- checkpoints, run lists, run counts -- is
             // proportional to the pairs of a launch: a batch beyond either bound is worked through in chunks of whole wavefronts, each an
             // ordinary sub-batch on the same stream (65M pairs at k = 32 wrapped the index; a huge batch asked for all of its
